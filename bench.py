@@ -19,6 +19,12 @@ scenarios per GPU in one resident sweep each.
 
 Prints ONE JSON line on rank 0.  Other modes: --config 1..4, --scenarios S (C5), --split P,
 --node-axis, --per-pod, --postfilter.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds what
+takes runs of its own: the rocprofv3 PMC traffic and SQ passes, the stamped latency profile, the
+CPU baseline and, on the default line, the `c3` / `c4_split` / `c5_sweep` / pct-0 legs (without
+it those fields are null / "not measured").  `--dump-outputs DIR` writes the last timed step's
+results (chosen nodes; the default mode also the node state they leave) as DIR/<name>.npy.
 """
 import argparse
 import csv
@@ -163,6 +169,30 @@ def cpu_baseline_scenarios(n_nodes, n_pods, seconds, threads, seed_of):
             "host": host, "pods_per_s": n_scen * n_pods / dt,
             "sample": f"{n_scen} C5 scenarios ({n_nodes} nodes x {n_pods} pods each, synthesis included), "
                       f"{threads} scenarios in parallel, {dt:.1f} s wall, oracle/kss_oracle.c single-threaded per scenario"}
+
+
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all files of one run together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: what the timed path handed back in its last step, one DIR/<name>.npy
+    per array, float64 (every int32 / int64 quantity here is below 2^53, so nothing is rounded).
+    An array beyond its share of DUMP_BYTES_MAX is written as a fixed sample: the elements at
+    sorted indices drawn once from a generator seeded by the array's name and size, the same
+    in every run and every build."""
+    import zlib
+
+    import numpy as np
+    if not path:
+        return
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // 8 // max(len(arrays), 1)  # float64 elements per array
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.size > share:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), a.size])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def num_feasible_nodes_to_find(n: int, pct: int) -> int:
@@ -358,6 +388,7 @@ def run_scenarios(args):
             "valu": valu_roofline(sq, kern_s, S * n_pods * n_nodes), "valu_detail": sq_detail,
             "cpu_baseline": cpu,
         }
+        dump_outputs(args.dump_outputs, {"chosen": chosen})
         print(json.dumps(out), flush=True)
     sweep.close()
     for x in synths:
@@ -457,6 +488,7 @@ def run_node_axis(args):
                          "note": "per pod the path is latency-bound: 2 launches + 2 collectives"},
             "cpu_baseline": None,
         }
+        dump_outputs(args.dump_outputs, {"chosen": chosen.cpu().numpy()})
         print(json.dumps(out), flush=True)
     sch.close()
     s.close()
@@ -576,6 +608,7 @@ def run_split(args):
             "cpu_baseline": cpu,
             "gpu_over_cpu": gpu_over_cpu(scheduled * args.steps / elapsed, cpu),
         }
+        dump_outputs(args.dump_outputs, {"chosen": chosen})
         print(json.dumps(out), flush=True)
     if world > 1 or parts > 1:
         runner.close()
@@ -828,6 +861,7 @@ def run_per_pod(args):
         "geometry": ctx.last_geometry(),
         "pods_scheduled": int(sum(1 for c in chosen if c >= 0)),
     }
+    dump_outputs(args.dump_outputs, {"chosen": np.array(chosen)})
     print(json.dumps(out), flush=True)
     ctx.close()
     s.close()
@@ -889,6 +923,7 @@ def run_snapshot(args):
         "scheduled": int((chosen >= 0).sum()),
         "read_and_compile_s_once": compile_s,
     }
+    dump_outputs(args.dump_outputs, {"chosen": chosen})
     print(json.dumps(out), flush=True)
     ctx.close()
 
@@ -984,6 +1019,7 @@ def run_postfilter(args):
         "compile_s": t_gen,
         "cpu_baseline": cpu,
     }
+    dump_outputs(args.dump_outputs, {"nominated": np.array([nominated_of[j] for j in unsched])})
     print(json.dumps(out), flush=True)
     ctx.close()
 
@@ -1086,7 +1122,7 @@ def child_leg(args, world: int, rank: int, local: int, dist, mode, label, timeou
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(int(port.item())))
     cmd = [sys.executable, os.path.abspath(__file__), *mode,
            "--steps", str(max(args.steps, 3)), "--warmup", str(max(args.warmup, 1)),
-           "--cpu-seconds", str(cpu_seconds)]
+           "--cpu-seconds", str(cpu_seconds), "--full"]
     if args.no_cpu:
         cmd.append("--no-cpu")
     if traffic and args.no_traffic:
@@ -1152,7 +1188,14 @@ def main():
     ap.add_argument("--snapshot", action="store_true",
                     help="the simulator's snapshot path: a ResourcesForSnap JSON read back, compiled, scheduled "
                          "with the profile the simulator's config gives (percentageOfNodesToScore 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: PMC traffic and SQ passes, the stamped latency "
+                         "profile, the CPU baseline and (default line) the C3 / C4 / C5 / pct-0 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_traffic = args.no_latency = args.no_legs = True
     if args.inner:
         args.no_cpu = args.no_traffic = args.no_latency = args.no_legs = True
     if args.no_legs:
@@ -1309,6 +1352,10 @@ def main():
             "c2_pct0": c2p0,
             "c3_pct0": c3p0,
         }
+        if args.dump_outputs:  # the last timed step's chosen nodes, and the node state it left on the device
+            st = ctx.node_state()
+            dump_outputs(args.dump_outputs, {"chosen": chosen[:n_pods], "node_requested": st["requested"],
+                                             "node_nonzero": st["nonzero"], "node_pod_count": st["pod_count"]})
         print(json.dumps(out), flush=True)
     ctx.close()
     s.close()

@@ -16,7 +16,7 @@ tail -2 gpurun_out/pytest_exp.log
 if [ "$CFG" = perpod ]; then mode="--per-pod --steps 1 --warmup 1"; else mode="--config $CFG --steps 3 --warmup 1"; fi
 for i in 1 2; do
   for lib in base $LIBS; do
-    KSS_LIB=$lib timeout -k 10 300 python -u bench.py $mode --no-cpu --no-traffic --no-c4 \
+    KSS_LIB=$lib timeout -k 10 300 python -u bench.py $mode --full --no-cpu --no-traffic --no-c4 \
       > gpurun_out/exp_$lib$i.json 2> gpurun_out/exp_$lib$i.err || exit $?
     python - "$lib" "gpurun_out/exp_$lib$i.json" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@
 #   tests        pytest -m gpu (whole suite; PYTEST_K narrows it with -k, PYTEST_TIMEOUT per test, default 120 s)
 #   svc          the service-grid tests alone (45 s per test)
 #   smoke        __graft_entry__.smoke()
-#   bench        the default line (C2 + c4_split leg, CPU baseline, PMC traffic, latency)
+#   bench        the default line with --full (C2 + the legs, CPU baseline, PMC traffic, latency)
 #   gpus2        bench.py --gpus 2 (on a 1-GPU box: must refuse with "2 GPUs requested")
 #   c1 c3 c4     bench.py --config 1 / 3 / 4
 #   c5           bench.py --scenarios 512 (C5 share of one GPU)
@@ -53,17 +53,17 @@ run_step() {
              > "$O/${tag}_pytest_svc.log" 2>&1; local rc=$?
            tail -3 "$O/${tag}_pytest_svc.log"; return $rc ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/${tag}_smoke.log" 2>&1 ;;
-    bench) timeout -k 10 700 python -u bench.py > "$O/${tag}_bench.json" 2> "$O/${tag}_bench.err"; local rc=$?
+    bench) timeout -k 10 700 python -u bench.py --full > "$O/${tag}_bench.json" 2> "$O/${tag}_bench.err"; local rc=$?
            tail -c 600 "$O/${tag}_bench.json"; return $rc ;;
     gpus2) timeout -k 10 120 python -u bench.py --gpus 2 > "$O/${tag}_gpus2.out" 2>&1
            local rc=$?; cat "$O/${tag}_gpus2.out"; [ $rc -eq 2 ] ;;
-    c1) timeout -k 10 300 python -u bench.py --config 1 --steps 20 --warmup 5 > "$O/${tag}_c1.json" 2> "$O/${tag}_c1.err" ;;
-    c3) timeout -k 10 500 python -u bench.py --config 3 > "$O/${tag}_c3.json" 2> "$O/${tag}_c3.err" ;;
-    c4) timeout -k 10 600 python -u bench.py --config 4 > "$O/${tag}_c4.json" 2> "$O/${tag}_c4.err" ;;
-    c5) timeout -k 10 500 python -u bench.py --scenarios 512 --steps 3 --warmup 1 > "$O/${tag}_c5.json" 2> "$O/${tag}_c5.err" ;;
+    c1) timeout -k 10 300 python -u bench.py --full --config 1 --steps 20 --warmup 5 > "$O/${tag}_c1.json" 2> "$O/${tag}_c1.err" ;;
+    c3) timeout -k 10 500 python -u bench.py --full --config 3 > "$O/${tag}_c3.json" 2> "$O/${tag}_c3.err" ;;
+    c4) timeout -k 10 600 python -u bench.py --full --config 4 > "$O/${tag}_c4.json" 2> "$O/${tag}_c4.err" ;;
+    c5) timeout -k 10 500 python -u bench.py --full --scenarios 512 --steps 3 --warmup 1 > "$O/${tag}_c5.json" 2> "$O/${tag}_c5.err" ;;
     split2) timeout -k 10 300 python -u bench.py --split 2 --steps 3 --warmup 1 --no-cpu > "$O/${tag}_split2.json" 2> "$O/${tag}_split2.err" ;;
     perpod) timeout -k 10 300 python -u bench.py --per-pod --steps 1 --warmup 1 > "$O/${tag}_perpod.json" 2> "$O/${tag}_perpod.err" ;;
-    postfilter) timeout -k 10 400 python -u bench.py --postfilter --steps 2 --warmup 1 > "$O/${tag}_postfilter.json" 2> "$O/${tag}_postfilter.err" ;;
+    postfilter) timeout -k 10 400 python -u bench.py --full --postfilter --steps 2 --warmup 1 > "$O/${tag}_postfilter.json" 2> "$O/${tag}_postfilter.err" ;;
     prof_c2) prof prof_c2 300 --steps 5 --warmup 1 ;;
     prof_c3) prof prof_c3 300 --config 3 --steps 3 --warmup 1 ;;
     prof_c4) prof prof_c4 400 --config 4 --steps 2 --warmup 1 ;;
