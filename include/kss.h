@@ -58,6 +58,7 @@ extern "C" {
 #define KSS_RES_SCALAR0 3
 #define KSS_NRES 7
 #define KSS_MAX_SCALAR 4
+#define KSS_MAX_SHAPES 64 /* resource shapes of a batch on k_simple's shape table */
 
 /* ---- filter plugins, in default MultiPoint order -------------------------
  * (simulator/scheduler/config/plugin_test.go:15-36).  A node's verdict is the
@@ -776,6 +777,14 @@ int kss_last_geometry(kss_ctx* ctx, int32_t* out3);
  * KSS_XCD=0 disables it), out2[1] = the chunks that found fewer workgroups on that XCD than shards
  * and ran again on an unrestricted grid (correctness never rests on placement). */
 int kss_last_xcd_local(kss_ctx* ctx, int32_t* out2);
+/* k_simple's shape table in the last run: out2[0] = the resource shapes in the table (0: the
+ * batch ran without it), out2[1] = evaluation rounds per refresh.  A default-profile batch
+ * without window and extended resources, with at most KSS_MAX_SHAPES distinct resource shapes
+ * (kss_plan_shapes) on a per-wave geometry of two or more waves keeps the state-dependent filter
+ * verdict and scores of every (shape, node) in LDS and re-evaluates only the committed node per
+ * pod.  Option "shape_table": 1 (default) grids of two or more shards, 2 also a single shard (no
+ * exchange hides the re-evaluation there: slower, for tests), 0 never. */
+int kss_last_shape_table(kss_ctx* ctx, int32_t* out2);
 /* kernel of the last scheduling launch: 0 general (k_schedule), 1 compact (k_simple:
  * batches without spread / inter-pod programs and without a record), 2 k_spread (batches
  * with programs, without a record), 3 k_preempt (kss_postfilter_pod); <0 on error */
@@ -886,6 +895,12 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3);
  * k_spread; a profile that scores an extended resource on a cluster that has them rules out both
  * loop kernels (out3[1] = the pod, out3[2] the reason). */
 int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_profile* prof, int32_t* out3);
+/* Host only: the resource shape of every pod of `ps` as a staged batch numbers them: ids[i]
+ * (ps->n_pods entries) counts from 0 in order of first appearance, *n = the shape count.  Two pods
+ * share a shape when their NodeResourcesFit request, LeastAllocated and BalancedAllocation
+ * requests (cpu, memory, ephemeral-storage) and "every request is zero" agree exactly; n_scalar:
+ * the cluster's extended resources.  KSS_E_UNSUPPORTED when the batch has no compact records. */
+int kss_plan_shapes(const kss_podset* ps, int32_t n_scalar, int32_t* ids, int32_t* n);
 const char* kss_plan_reason(int32_t code);
 /* Test support: y[i] = the device restatement of Go math.Log (kss_spread.cuh go_log_dev,
  * PodTopologySpread's topologyNormalizingWeight in k_spread) at x[i], i < n, evaluated on

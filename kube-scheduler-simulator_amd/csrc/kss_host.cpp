@@ -10,11 +10,42 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <map>
 #include <numeric>
 #include <string>
 #include <vector>
 
 #include "kss_host.h"
+
+kss_shape_key kss_host_shape_key(const double fit_req[3], const double snz[3], const double sreq[3], bool all_zero) {
+  kss_shape_key k;
+  std::memcpy(&k.w[0], fit_req, 3 * sizeof(double));
+  std::memcpy(&k.w[3], snz, 3 * sizeof(double));
+  std::memcpy(&k.w[6], sreq, 3 * sizeof(double));
+  k.w[9] = all_zero ? 1 : 0;
+  return k;
+}
+
+int kss_host_assign_shapes(const kss_shape_key* keys, int n, int32_t* ids, int32_t* rep) {
+  struct Less {
+    bool operator()(const kss_shape_key& a, const kss_shape_key& b) const {
+      return std::lexicographical_compare(a.w, a.w + 10, b.w, b.w + 10);
+    }
+  };
+  std::map<kss_shape_key, int32_t, Less> seen;
+  for (int i = 0; i < n; i++) {
+    auto it = seen.find(keys[i]);
+    if (it == seen.end()) {
+      const int32_t id = (int32_t)seen.size();
+      it = seen.emplace(keys[i], id).first;
+      rep[id] = i;
+    }
+    ids[i] = it->second;
+  }
+  const int ns = (int)seen.size();
+  for (int j = ns; j < n; j++) rep[j] = -1;
+  return ns;
+}
 
 double kss_go_log(double x) {
   const double Ln2Hi = 6.93147180369123816490e-01, Ln2Lo = 1.90821492927058770002e-10;

@@ -24,3 +24,15 @@ int kss_host_format(const kss_host_names* names, const kss_profile* prof, const 
 // The PreFilterResult node set of ps->pods[i] (KSS_E_INVAL on a bad index or list); *has = 0 when
 // the pod's PreFilter returned none.
 int kss_host_prefilter_nodes(const kss_podset* ps, int32_t i, int n_nodes, std::vector<int>* out, int* has);
+
+// Resource shapes of a batch (k_simple's shape table, kss_simple.cuh): what the state-dependent
+// part of an evaluation reads of a pod -- the NodeResourcesFit request, the LeastAllocated and
+// BalancedAllocation requests and whether the whole request is zero.  Two pods share a shape when
+// these agree bit for bit (the doubles' bit patterns, so -0.0 and 0.0 differ).
+struct kss_shape_key {
+  uint64_t w[10];
+};
+kss_shape_key kss_host_shape_key(const double fit_req[3], const double snz[3], const double sreq[3], bool all_zero);
+// ids[i] = the shape of keys[i], numbered from 0 by first appearance; rep[j] = the first pod of
+// shape j (rep: n entries, the ones past the shape count set to -1).  Returns the shape count.
+int kss_host_assign_shapes(const kss_shape_key* keys, int n, int32_t* ids, int32_t* rep);

@@ -65,7 +65,7 @@ enum KssOpt {
   O_SHARDS, O_XCD, O_XCD_SHARDS, O_NO_SIMPLE, O_NO_SPREAD, O_AXIS_BLOCKS, O_AXIS_NO_FOLD, O_NODES_PER_SHARD,
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
-  O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_N
+  O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE, O_N
 };
 struct OptDef {
   const char* name;
@@ -101,6 +101,7 @@ const OptDef kOptDefs[O_N] = {
     {"xcd_force_fallback", "KSS_XCD_FORCE_FALLBACK", 0},  // XCD-local launches report failed placement
     {"spread_two_level", "KSS_SPREAD_TWO_LEVEL", 1},      // k_spread at W > 64: 1 two-level selectHost exchange, 2 + reductions
     {"spread_lb256", "KSS_SPREAD_LB256", 1},              // k_spread compiled for <= 256 lanes when the shard fits
+    {"shape_table", "KSS_SHAPE_TABLE", 1},                // k_simple's shape table: 1 sharded grids that admit it, 2 also one shard, 0 never
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -350,6 +351,33 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple(const DevJob* __rest
   else
     simple_schedule<DEF, false, WIN>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen, job.meta,
                                      P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor);
+}
+
+// k_simple<true, false> in per-wave mode with the shape table (simple_schedule_tab): a kernel of
+// its own, so the kernels above keep their register allocation.  Same arguments (launch_simple
+// passes one argument list); n_shapes takes k_find's place.  The host launches it only for a
+// geometry in per-wave mode with at least two waves.
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab(const DevJob* __restrict__ jobs, kss_profile prof, int W,
+                                                                int cap, int k0, int k1, unsigned long long* gran, int* err,
+                                                                unsigned long long* stamps, XPeers X, unsigned epoch0,
+                                                                int stat_row0, int n_shapes) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  const int Wl = X.n > 1 ? X.wl : W;
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  int xs = 0;
+  if (X.xcd_local) {  // as k_simple
+    if (threadIdx.x == 0)
+      H.pad[0] = xcd_slot(reinterpret_cast<int*>(gran + 2 * (size_t)W * SX_VALS), W, (int)gridDim.x, err, X.xcd_local == 2);
+    __syncthreads();
+    xs = H.pad[0];
+    if (xs < 0) return;
+  }
+  const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
+  const DevJob job = jobs[ji];
+  unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  simple_schedule_tab(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w, cap, g, X,
+                      epoch0, err, ji == 0 ? stamps : nullptr, smem, n_shapes);
 }
 
 // grid = W (one cluster); each shard's nodes live in LDS (cap slots); bins_cap: histogram +
@@ -778,6 +806,8 @@ struct kss_ctx {
   bool xcd_mode = true;       // KSS_XCD=0: no XCD-local k_simple grids
   int xcd_w = 0;              // KSS_XCD_SHARDS: shards of an XCD-local grid (tuning; default: CUs per XCD)
   int last_xcd[2] = {0, 0};   // the last run: XCD-local grid used, chunks that fell back to an unrestricted grid
+  int spod_shapes = 0;        // resource shapes of the staged pods (build_spods)
+  int last_shape[2] = {0, 0};  // the last run: shapes in k_simple's table (0: not used), rounds per refresh
   int nodes_per_shard = 128;  // KSS_NODES_PER_SHARD (C2 sweep: 128 > 256 > 512 nodes per shard)
   int pref_threads = 256;     // KSS_THREADS
   PlanNeeds staged_need;
@@ -1146,13 +1176,28 @@ bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q) {
 
 // Compact records of every pod of a (validated) podset for k_simple; false when some pod
 // needs another kernel (spread / inter-pod-affinity programs, or fill_spod refuses it).
-bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out) {
+// n_shapes (optional): the batch's resource shapes (SPod::shape, SPod::shape_rep).
+bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr) {
   out.assign((size_t)std::max(ps->n_pods, 1), SPod{});
+  if (n_shapes) *n_shapes = 0;
   for (int i = 0; i < ps->n_pods; i++) {
     const kss_pod& p = ps->pods[i];
     if (p.n_hard | p.n_soft | p.ipa_len) return false;
     if (!fill_spod(ps, p, n_scalar, out[(size_t)i])) return false;
   }
+  const int n = ps->n_pods;
+  std::vector<kss_shape_key> keys((size_t)n);
+  std::vector<int32_t> ids((size_t)n), rep((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const SPod& q = out[(size_t)i];
+    keys[(size_t)i] = kss_host_shape_key(q.fit_req, q.snz, q.sreq, (q.flags & SP_ALLZERO) != 0);
+  }
+  const int ns = kss_host_assign_shapes(keys.data(), n, ids.data(), rep.data());
+  for (int i = 0; i < n; i++) {
+    out[(size_t)i].shape = ids[(size_t)i];
+    out[(size_t)i].shape_rep = rep[(size_t)i];
+  }
+  if (n_shapes) *n_shapes = ns;
   return true;
 }
 
@@ -2674,6 +2719,18 @@ static bool simple_fits(const Geometry& g, int nsc) {
          simple_lds_bytes(simple_cap(g), nsc) <= KSS_LDS_BUDGET;
 }
 
+// k_simple's shape table (k_simple_tab) for a batch of n_shapes resource shapes on geometry g:
+// the default profile, no window (k_find 0), no extended resources, per-wave mode with at least
+// two waves, at most KSS_MAX_SHAPES shapes, and the table within the LDS budget.  One shard has no
+// exchange for the refresh to hide behind and measured slower with the table (C1): only
+// on request (option shape_table = 2).
+static bool shape_table_ok(const Geometry& g, int n_nodes, int n_shapes, const kss_profile& prof, int k_find, int nsc) {
+  const int per = (n_nodes + g.W - 1) / std::max(g.W, 1), nwave = g.threads / 64;
+  return (g.W > 1 || opt(O_SHAPE_TABLE) >= 2) && n_shapes >= 1 && n_shapes <= KSS_MAX_SHAPES && k_find == 0 && nsc == 0 && nwave >= 2 && KSS_SIMPLE_PW &&
+         per <= PW_LANES * nwave && same_profile(prof, default_profile_c()) &&
+         simple_lds_bytes(simple_cap(g), 0, n_shapes) <= KSS_LDS_BUDGET;
+}
+
 // Extended (scalar) resources on k_simple / k_spread: their NodeResourcesFit filter and
 // AssumePod run in LDS; a profile that scores one (fit / BalancedAllocation resources past
 // ephemeral-storage) keeps the batch on k_schedule.
@@ -2765,18 +2822,23 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          int n_pods_max, int max_nodes, int chunk, unsigned long long* gran, size_t gran_bytes, int* err,
                          unsigned long long* stamps = nullptr, hipEvent_t* ev = nullptr, const SplitRun* split = nullptr,
                          int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
-                         hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0) {
+                         hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
+                         int n_shapes = 0) {
   // st2 (with pev, two events per chunk): the static words of chunk i+1 are computed on st2 into the
   // other half of a double-buffered table while k_simple runs chunk i on st (each job's table holds
   // 2 x chunk rows); k_simple of chunk i waits for its k_static, k_static of chunk i+1 for
   // k_simple of chunk i-1 (the last reader of that half)
   int cap = simple_cap(g);
-  const size_t shmem = simple_lds_bytes(cap, nsc);
   const bool def = same_profile(prof, default_profile_c());
   // k_find > 0: the percentageOfNodesToScore window (one job, not split)
   const bool win = k_find > 0;
-  const void* fn = win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
-                       : (def ? (const void*)k_simple<true, false> : (const void*)k_simple<false, false>);
+  // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
+  const bool tab = n_shapes > 0 && def && !win && nsc == 0;
+  const size_t shmem = simple_lds_bytes(cap, nsc, tab ? n_shapes : 0);
+  const void* fn = tab   ? (const void*)k_simple_tab
+                   : win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
+                         : (def ? (const void*)k_simple<true, false> : (const void*)k_simple<false, false>);
+  int last_arg = tab ? n_shapes : k_find;  // k_simple_tab: n_shapes in k_find's place
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   XPeers X = split ? split->X : XPeers{};
   const bool sp_grid = X.n > 1;
@@ -2828,7 +2890,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     }
     unsigned long long* sp = k0 == 0 ? stamps : nullptr;
     void* args[] = {(void*)&jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
-                    (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&k_find};
+                    (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg};
     const int ci = k0 / chunk;
     if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
     if (xcd) {
@@ -3317,10 +3379,16 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   }
   ctx->last_xcd[0] = (simple && xcd_try && g.W > 1) || xcd_spread ? 1 : 0;
   ctx->last_xcd[1] = 0;
+  // the shape table: the whole staged batch (its shape directory sits in its first records)
+  const int win_find = k_find < (int)N ? k_find : 0;
+  const bool tab = simple && opt(O_SHAPE_TABLE) && n == ctx->staged_n &&
+                   shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
+  ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;
+  ctx->last_shape[1] = tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
   if (simple)
     rc = launch_simple(ctx->stream, g, 1, jd, ctx->prof, n, (int)N, chunk, gran, gb,
                        errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr, ctx->dc.n_scalar, ctx->last_xcd[0] != 0,
-                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, k_find < (int)N ? k_find : 0);
+                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0);
   else if (spread)
   {
     const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar);
@@ -3445,7 +3513,7 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
     ctx->staged_max_own = std::max(ctx->staged_max_own, (int)ps->pods[i].own_terms_len);
     ctx->staged_names |= ps->pods[i].names_len >= 0;
   }
-  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host);
+  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes);
   ctx->gpod_ok = false;
   if (!ctx->spod_ok) {  // programs: the resolved records of k_spread
     ctx->gpod_ok = build_gpods(ps, ctx->dc.n_scalar, ctx->dc.n_classes, ctx->key_card_h.data(), ctx->key_flags_h.data(),
@@ -4416,6 +4484,24 @@ int kss_last_xcd_local(kss_ctx* ctx, int32_t* out2) {
   if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
   out2[0] = ctx->last_xcd[0];
   out2[1] = ctx->last_xcd[1];
+  return 0;
+}
+
+int kss_last_shape_table(kss_ctx* ctx, int32_t* out2) {
+  if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
+  out2[0] = ctx->last_shape[0];
+  out2[1] = ctx->last_shape[1];
+  return 0;
+}
+
+int kss_plan_shapes(const kss_podset* ps, int32_t n_scalar, int32_t* ids, int32_t* n) {
+  if (!ps || !n || ps->n_pods < 0 || (ps->n_pods > 0 && (!ids || !ps->pods)) || n_scalar < 0 || n_scalar > KSS_MAX_SCALAR)
+    return fail(KSS_E_INVAL, "bad arguments");
+  std::vector<SPod> sp;
+  int ns = 0;
+  if (!build_spods(ps, n_scalar, sp, &ns)) return fail(KSS_E_UNSUPPORTED, "the batch has no compact records (k_simple does not take it)");
+  for (int i = 0; i < ps->n_pods; i++) ids[i] = sp[(size_t)i].shape;
+  *n = ns;
   return 0;
 }
 

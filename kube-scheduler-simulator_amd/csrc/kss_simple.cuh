@@ -190,11 +190,16 @@ struct SPod {
   int32_t status;      // kss_pod.prefilter_status
   int32_t cls;         // class_count row the pod joins (-1 none)
   int32_t own_off, own_len;  // term_count rows it adds: ints[own_off .. +own_len) of the staged pool
-  int32_t pad[3];
+  // resource shape (build_spods, kss_host.h assign_shapes): pods whose fit_req / snz / sreq / SP_ALLZERO
+  // agree bit for bit share an id, numbered by first appearance; record j < (shapes of the batch)
+  // also names the first pod of shape j (the shape directory the table kernel stages from)
+  int32_t shape, shape_rep;
+  int32_t pad;
   int64_t sc_fit[KSS_MAX_SCALAR];  // NodeResourcesFit PreFilter request of each extended (scalar) resource
   int64_t sc_req[KSS_MAX_SCALAR];  // AssumePod Requested delta of each scalar resource
 };
 static_assert(sizeof(SPod) % 16 == 0, "SPod is copied as uint4");
+static_assert(sizeof(SPod) == 144 + 16 * KSS_MAX_SCALAR, "the shape words took SPod's padding: no growth");
 
 // Static word of one (pod, node):
 //   bits 0-2   the first failing static filter: 0 pass, 1-4 KSS_F_NODE_UNSCHEDULABLE ..
@@ -919,9 +924,62 @@ constexpr int RING = 4;                // record / static-word ring slots
 constexpr int CV_EXTRA = MAXWAVES;     // H1 slots past the shard's nodes: one per wave (per-wave mode)
 constexpr int PW_LANES = 63;           // per-wave mode: node slots per wave (lane 63 is the wave's H1 lane)
 
-__host__ __device__ inline size_t simple_lds_bytes(int cap, int nsc = 0) {
-  return sizeof(SimpleHdr) + RING * sizeof(SPod) + (size_t)cap * (8 * 8 + 3 * 8 + 2 * 4 + RING * 4 + 16 * (size_t)nsc) +
-         20 * ((size_t)cap + CV_EXTRA);
+// The shape table of k_simple_tab (simple_schedule_tab): for every resource shape c of the batch
+// and every node slot s, the packed state-dependent result of dyn_eval_def(shape c, row s).
+// (KSS_MAX_SHAPES shapes at most: kss.h)
+struct SShape {  // what dyn_eval_def reads of a pod
+  double fit_req[3], snz[2], sreq[2];
+  int32_t flags, pad;
+};
+static_assert(sizeof(SShape) == 64, "SShape: 64 B");
+constexpr int SSHAPE_WORDS = (int)(sizeof(SShape) / 8);
+constexpr uint32_t ST_FITS = 1u << 16;  // table word: NodeResourcesFit passes, Fit score << 8, BalancedAllocation score
+// a table row holds cap slots at a stride of cap + 1 words: the lanes that copy a pending row into
+// one slot's column (lane = shape) then fall into different LDS banks
+__host__ __device__ inline size_t shape_tab_bytes(int cap, int n_shapes) {
+  return n_shapes > 0 ? (size_t)n_shapes * sizeof(SShape) + 4 * (size_t)MAXWAVES * KSS_MAX_SHAPES +
+                            4 * (size_t)n_shapes * ((size_t)cap + 1)
+                      : 0;
+}
+// rounds of one refresh: candidates x shapes evaluations on the lanes of every wave but wave 0
+__host__ __device__ inline int shape_tab_rounds(int nwave, int n_shapes) {
+  const int idle = 64 * (nwave - 1);
+  return idle > 0 ? (nwave * n_shapes + idle - 1) / idle : 0;
+}
+
+__host__ __device__ inline size_t simple_lds_bytes(int cap, int nsc = 0, int n_shapes = 0) {
+  const size_t base = sizeof(SimpleHdr) + RING * sizeof(SPod) +
+                      (size_t)cap * (8 * 8 + 3 * 8 + 2 * 4 + RING * 4 + 16 * (size_t)nsc) + 20 * ((size_t)cap + CV_EXTRA);
+  return n_shapes > 0 ? (base + 15) / 16 * 16 + shape_tab_bytes(cap, n_shapes) : base;
+}
+
+struct ShapeTab {
+  uint64_t* shp;   // [SSHAPE_WORDS][n_shapes]: the shapes' SShape records, staged once per launch, word by word
+                   // (lane = shape reads consecutive words: no bank conflict)
+  uint32_t* pnd;   // [MAXWAVES][KSS_MAX_SHAPES]: wave v's candidate with the pod committed, per shape
+  uint32_t* T;     // [n_shapes][ts]
+  int n, ts;       // shapes, row stride (cap + 1)
+};
+__device__ __forceinline__ SShape shape_get(const ShapeTab& t, int j) {
+  uint64_t w[SSHAPE_WORDS];
+#pragma unroll
+  for (int i = 0; i < SSHAPE_WORDS; i++) w[i] = t.shp[i * t.n + j];
+  SShape q;
+  __builtin_memcpy(&q, w, sizeof(SShape));
+  return q;
+}
+__device__ __forceinline__ ShapeTab shape_tab_view(uint8_t* smem0, int cap, int n_shapes) {
+  uint8_t* b = smem0 + (simple_lds_bytes(cap, 0) + 15) / 16 * 16;
+  ShapeTab t;
+  t.n = n_shapes;
+  t.ts = cap + 1;
+  t.shp = reinterpret_cast<uint64_t*>(b);
+  t.pnd = reinterpret_cast<uint32_t*>(b + (size_t)n_shapes * sizeof(SShape));
+  t.T = t.pnd + MAXWAVES * KSS_MAX_SHAPES;
+  return t;
+}
+__device__ __forceinline__ uint32_t shape_pack(const SVal& e) {
+  return (e.f == 0 ? ST_FITS : 0u) | (((uint32_t)e.fit & 0xFFu) << 8) | ((uint32_t)e.ba & 0xFFu);
 }
 
 __device__ __forceinline__ SimpleShard shard_view(uint8_t* base, int cap, int nsc) {
@@ -1009,7 +1067,9 @@ __device__ __forceinline__ int32_t least_bf(double requested, double capacity, d
 // with weights 1 / 1, BalancedAllocation over cpu / memory), branch-free: every lane
 // computes every score and selects, so the node loop carries no exec-mask regions.  The
 // scores of an infeasible node are not read (pass B skips it).
-__device__ __forceinline__ SVal dyn_eval_def(const SPod& q, uint32_t w, const DynRow& r) {
+// Q: SPod, or the resource shape alone (SShape: the same fields under the same names).
+template <class Q>
+__device__ __forceinline__ SVal dyn_eval_def(const Q& q, uint32_t w, const DynRow& r) {
   const int code = sw_code(w);
   bool bad = (int64_t)r.pods + 1 > (int64_t)r.allowed;
   const bool rq = !(q.flags & SP_ALLZERO);
@@ -2157,6 +2217,264 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     st_ag(&c.nonzero[N + n], (int64_t)L.r64[7 * cap + s]);
     st_ag(&c.pod_count[n], L.r32[s]);
     for (int i = 0; i < L.nsc; i++) st_ag(&c.requested[(size_t)(3 + i) * N + n], L.sc[(size_t)(L.nsc + i) * cap + s]);
+  }
+  handoff_release();
+}
+
+// simple_schedule<true, true, false> with the shape table (k_simple_tab): the default profile,
+// per-wave mode with at least two waves, no window, no extended resources, and a batch of at most
+// KSS_MAX_SHAPES resource shapes (SPod::shape).  The state-dependent part of an evaluation --
+// the NodeResourcesFit verdict and the Fit / BalancedAllocation scores -- depends on the node's
+// row and the pod's shape only, and a commit changes one row.  So the shard keeps
+//   T[c][s] = dyn_eval_def(shape c, row s), packed (shape_pack), for every shape c and slot s,
+// and a pod reads its values instead of evaluating them:
+//   pass B of pod k      T[shape(k)][s] and the pod's static word -> the selectHost key;
+//   statistics of k+1    H0 from T[shape(k+1)][s]; H1 (the wave's candidate with pod k added) needs
+//                        the filter verdict only: the pod count and three resource comparisons;
+//   refresh              while wave 0 exchanges, the other waves evaluate every shape on every wave's
+//                        candidate row with pod k added (candidates x shapes lane-jobs, 64 per wave
+//                        and round) into the pending rows pnd[wave][shape];
+//   after the closing barrier, the wave that owns the winner's slot commits pod k on its row and
+//                        copies pnd[that wave][c] to T[c][slot].
+// Invariant: after pod k's commit and copy, T[c][s] is the evaluation on the committed state.
+// Ordering.  A slot's T entries and, between the barriers below, its row are written by the
+// wave that owns the slot only, and T is read by that wave only: program order.  The rows are
+// read by other waves in the refresh, between the statistics barrier and the closing barrier
+// of a pod, and written (the commit) between the closing barrier and the next statistics
+// barrier; pnd is written in the first interval and read in the second.  (So the commit is not
+// wave 0's, before the closing barrier, as in simple_sync_pw's own: commit = false there.)
+static_assert(!KSS_PW_ALLPOLL, "the shape table rests on simple_sync_pw's closing barrier");
+__device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __restrict__ spods,
+                                                    const uint32_t* __restrict__ stat, int k0, int k1, int n_pods,
+                                                    int32_t* chosen, PodMeta* meta, int W, int w, int cap,
+                                                    unsigned long long* gran, const XPeers& X, unsigned epoch0, int* err,
+                                                    unsigned long long* stamps, long long* smem, int n_shapes) {
+  constexpr kss_profile prof = default_profile_c();
+  constexpr int PD = 3;  // prefetch distance of per-wave mode (simple_schedule)
+  constexpr int NQ = (int)(sizeof(SPod) / 16);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const SimpleShard L = shard_view(reinterpret_cast<uint8_t*>(smem) + sizeof(SimpleHdr), cap, 0);
+  const ShapeTab TB = shape_tab_view(reinterpret_cast<uint8_t*>(smem), cap, n_shapes);
+  const size_t N = (size_t)c.N;
+  const int per = (c.N + W - 1) / W;
+  const int lo = min(c.N, w * per), hi = min(c.N, lo + per), own = hi - lo;
+  if (k1 <= k0) return;
+  const int nwave = nt >> 6, lane = tid & 63, wv = tid >> 6;
+  const int pwv = (own + nwave - 1) / nwave;  // the wave's node slots (<= PW_LANES)
+  const int s = wv * pwv + lane;              // this lane's slot
+  const bool mine = lane < pwv && s < own;
+  // shard rows, reciprocals, static words and records of pods k0 .. k0 + PD - 1, the shapes -> LDS
+  handoff_acquire();
+  for (int i = tid; i < own; i += nt) {
+    const int n = lo + i;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const int64_t A = c.alloc[k * N + n];
+      L.r64[k * cap + i] = (double)A;
+      L.r64[(3 + k) * cap + i] = (double)ld_ag(&c.requested[k * N + n]);
+      L.inv[k * cap + i] = A > 0 ? 1.0 / (double)A : 0.0;
+    }
+    L.r64[6 * cap + i] = (double)ld_ag(&c.nonzero[n]);
+    L.r64[7 * cap + i] = (double)ld_ag(&c.nonzero[N + n]);
+    L.r32[i] = ld_ag(&c.pod_count[n]);
+    L.r32[cap + i] = c.allowed_pods[n];
+    for (int d = 0; d < PD && k0 + d < k1; d++) L.st[((k0 + d) % RING) * cap + i] = ld_ag(&stat[(size_t)d * N + lo + i]);
+  }
+  for (int i = tid; i < min(k1 - k0, PD) * NQ; i += nt) {
+    const int j = k0 + i / NQ;
+    reinterpret_cast<uint4*>(L.ring + j % RING)[i % NQ] = reinterpret_cast<const uint4*>(spods + j)[i % NQ];
+  }
+  for (int j = tid; j < n_shapes; j += nt) {  // record j names the first pod of shape j
+    const SPod& r = spods[min(max(spods[j].shape_rep, 0), n_pods - 1)];
+    SShape d;
+#pragma unroll
+    for (int i = 0; i < 3; i++) d.fit_req[i] = r.fit_req[i];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+      d.snz[i] = r.snz[i];
+      d.sreq[i] = r.sreq[i];
+    }
+    d.flags = r.flags;
+    d.pad = 0;
+    uint64_t dw[SSHAPE_WORDS];
+    __builtin_memcpy(dw, &d, sizeof(SShape));
+#pragma unroll
+    for (int i = 0; i < SSHAPE_WORDS; i++) TB.shp[i * n_shapes + j] = dw[i];
+  }
+  if (tid == 0) H.abort = 0;
+  __syncthreads();
+  if (mine) {  // the table of the loaded state: every shape on the lane's own slot
+    const DynRow r = shard_row(L, s);
+    for (int j = 0; j < n_shapes; j++) TB.T[j * TB.ts + s] = shape_pack(dyn_eval_def(shape_get(TB, j), 0u, r));
+  }
+  __syncthreads();
+
+  KSS_GLOBAL const uint32_t* gstat = gp(stat);
+  KSS_GLOBAL const uint4* gspod = gp(reinterpret_cast<const uint4*>(spods));
+  KSS_GLOBAL unsigned long long* gstamps = gp(stamps);
+  long long R[4] = {0, 0, 0, 0};
+  // the outcome of pod pend_k, not yet stored (simple_schedule's deferred outcome: wave 1)
+  constexpr int out_tid = 64;
+  PodMeta pend{};
+  int pend_k = -1;
+  auto store_pending = [&]() {
+    if (pend_k < 0) return;
+    if (chosen) gp(chosen)[pend_k] = pend.chosen;
+    if (meta) {
+      KSS_GLOBAL PodMeta* mm = gp(meta) + pend_k;
+      mm->chosen = pend.chosen;
+      mm->n_feasible = pend.n_feasible;
+      mm->scored = pend.scored;
+      mm->status = pend.status;
+      mm->best_total = pend.best_total;
+    }
+    pend_k = -1;
+  };
+  int parity = 0;
+  unsigned epoch = epoch0;
+  const int kb = key_bits(prof, c.N);
+  // prefetch lanes as in simple_schedule
+  const int pf_w0 = (KSS_PF_LAST_WAVE && nwave >= 3) ? nwave - 1 : 1;
+  const bool pf_wave = __builtin_amdgcn_readfirstlane(tid >> 6) >= pf_w0;
+  uint4 pfq = make_uint4(0, 0, 0, 0);
+  uint32_t pfw[PF_MAX];
+#pragma unroll
+  for (int j = 0; j < PF_MAX; j++) pfw[j] = 0;
+  const int pf_lane = tid - 64 * pf_w0, pf_n = nt - 64 * pf_w0;
+  const int pf_per = (own + pf_n - 1) / pf_n;
+  // refresh jobs: job = round * idle lanes + this lane's index among them; job -> (wave v, shape j)
+  const int idle_n = 64 * (nwave - 1), jobs = nwave * n_shapes;
+  const int job0 = tid - 64;  // (waves 1.. only)
+  const int v0 = job0 >= 0 ? job0 / n_shapes : 0, j0 = job0 >= 0 ? job0 % n_shapes : 0;
+  // the shapes of pods k, k+1 (and k+2, read one pod ahead of its use)
+  int ck = 0, cn = min(max(L.ring[k0 % RING].shape, 0), n_shapes - 1), cnn = 0;
+  for (int k = k0 - 1; k < k1; k++) {
+    KSS_GLOBAL unsigned long long* sp = (stamps && k >= k0 && k - k0 < KSS_NSTAMP_PODS / 2)
+                                            ? gstamps + (size_t)w * 8 * KSS_NSTAMP_PODS + (size_t)(k - k0) * 16
+                                            : nullptr;
+    if (sp && tid == 0) sp[0] = wall_clock64();
+    if (sp && tid == 64) sp[9] = wall_clock64();
+    const SPod& pk = L.ring[(k + RING) % RING];
+    const SPod& qn = L.ring[(k + 1) % RING];
+    const int slk = (k + RING) % RING, sln = (k + 1) % RING;
+    if (k + 2 < k1) cnn = min(max(L.ring[(k + 2) % RING].shape, 0), n_shapes - 1);
+    const bool pf_on = pf_wave && k >= k0 && k + PD < k1 && own > 0;
+    if (pf_on) {
+      KSS_GLOBAL const uint4& src = gspod[(size_t)(k + PD) * NQ + min(pf_lane, NQ - 1)];
+      pfq = make_uint4(src.x, src.y, src.z, src.w);
+#pragma unroll
+      for (int j = 0; j < PF_MAX; j++)
+        if (j < pf_per) pfw[j] = ld_ag(&gstat[(size_t)(k + PD - k0) * N + lo + min(j * pf_n + pf_lane, own - 1)]);
+    }
+    const bool refresh_on = k >= k0 && k + 1 < k1;  // pod k may commit and a pod after it reads the table
+    // pass B: pod k's values from the table and its static word
+    const long long nf = R[1];
+    const int max_tt = (int)R[2], max_na = (int)R[3];
+    const bool scored = nf > 1;
+    const bool keys = k >= k0 && pk.status == 0 && nf > 0;
+    const float rtt = __builtin_amdgcn_rcpf((float)max(max_tt, 1));
+    const float rna = __builtin_amdgcn_rcpf((float)max(max_na, 1));
+    long long best = 0;
+    if (keys && mine) {
+      const uint32_t t = TB.T[ck * TB.ts + s], wd = L.st[slk * cap + s];
+      const SVal e{sw_code(wd), sw_tt(wd), sw_na(wd), (int)((t >> 8) & 0xFFu), (int)(t & 0xFFu)};
+      const long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s));
+      best = (e.f == 0 && (t & ST_FITS)) ? key : 0;
+    }
+    if (sp && tid == 0) sp[1] = wall_clock64();
+    best = wave_max_key(best, kb, c.node_base);
+    if (sp && tid == 0) sp[2] = wall_clock64();
+    const int cand = best ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)best) - c.node_base - lo : -1;
+    // statistics of pod k+1: H0 from the table; H1 on the wave's candidate with pod k added
+    uint32_t u[6] = {0, 0, 0, 0, 0, 0};
+    if (k + 1 < k1) {
+      const bool extra = lane == pwv && cand >= 0;
+      if (mine || extra) {
+        const int ns = extra ? cand : s;
+        const uint32_t wd = L.st[sln * cap + ns];
+        bool ok;
+        if (extra) {  // fitsRequest of pod k+1 on the row after AssumePod(pod k): the verdict alone
+          bool bad = (int64_t)L.r32[ns] + 2 > (int64_t)L.r32[cap + ns];
+          bool sh = false;
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+            sh |= qn.fit_req[i] > L.r64[i * cap + ns] - (L.r64[(3 + i) * cap + ns] + pk.creq[i]);
+          bad |= !(qn.flags & SP_ALLZERO) & sh;
+          ok = !bad;
+        } else {
+          ok = (TB.T[cn * TB.ts + s] & ST_FITS) != 0;
+        }
+        ok &= sw_code(wd) == 0;
+        const bool c0 = ok && !extra, c1 = ok && (extra || s != cand);
+        const uint32_t tt = (uint32_t)sw_tt(wd), na = (uint32_t)sw_na(wd);
+        u[0] = c0 ? 1u : 0u;
+        u[1] = c0 ? tt : 0u;
+        u[2] = c0 ? na : 0u;
+        u[3] = c1 ? 1u : 0u;
+        u[4] = c1 ? tt : 0u;
+        u[5] = c1 ? na : 0u;
+      }
+    }
+    if (sp && tid == 0) sp[3] = wall_clock64();
+    auto idle = [&]() {
+      // the refresh: waves 1.. (wave 0 exchanges), the waves' candidates from the reduction rows
+      // of this pod (parity not yet flipped), each on its row with pod k added
+      if (refresh_on && keys && wv > 0) {
+        for (int job = job0, rd = 0; job < jobs; job += idle_n, rd++) {
+          const int v = rd == 0 ? v0 : job / n_shapes, j = rd == 0 ? j0 : job % n_shapes;
+          const long long kv = H.red[parity][v][0];
+          if (kv == 0) continue;
+          const int cs = (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)kv) - c.node_base - lo;
+          DynRow r = shard_row(L, cs);
+          add_commit(r, pk);
+          TB.pnd[v * KSS_MAX_SHAPES + j] = shape_pack(dyn_eval_def(shape_get(TB, j), 0u, r));
+        }
+        if (sp && (tid == 64 || tid == 128)) sp[11 + (tid >> 6)] = wall_clock64();  // waves 1, 2: refresh done
+      }
+      if (pf_on) {  // the prefetched record and static words -> their ring slots (simple_schedule)
+        reinterpret_cast<uint4*>(L.ring + (k + PD) % RING)[min(pf_lane, NQ - 1)] = pfq;
+#pragma unroll
+        for (int j = 0; j < PF_MAX; j++)
+          if (j < pf_per) L.st[((k + PD) % RING) * cap + min(j * pf_n + pf_lane, own - 1)] = pfw[j];
+      }
+      if (tid == out_tid) store_pending();  // the previous pod's outcome
+    };
+    if (!simple_sync_pw(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, false, L, kb, R, sp,
+                        idle))
+      return;
+    if (sp && tid == 0) sp[5] = wall_clock64();
+    if (k >= k0) {
+      const long long K = R[0];
+      const int x = K ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)K) - c.node_base : -1;
+      // the wave that owns the winner's slot: AssumePod on its row, the pending row into the table
+      if (x >= lo && x < hi && (x - lo) / max(pwv, 1) == wv) {
+        simple_commit_lanes(L, pk, x - lo, lane);
+        if (refresh_on && lane < n_shapes) TB.T[lane * TB.ts + (x - lo)] = TB.pnd[wv * KSS_MAX_SHAPES + lane];
+      }
+      if (w == X.w_off && tid == out_tid) {
+        pend.chosen = K ? x + c.node_base : -1;
+        pend.n_feasible = (int)nf;
+        pend.scored = (K && scored) ? 1 : 0;
+        pend.status = pk.status != 0 ? (pk.status == KSS_PF_ERROR ? 3 : 2) : (nf == 0 ? 1 : 0);
+        pend.best_total = pend.scored ? (int64_t)((unsigned long long)K >> 32) : 0;
+        pend_k = k;
+      }
+    }
+    ck = cn;
+    cn = cnn;
+    if (sp && tid == 0) sp[6] = wall_clock64();
+  }
+  if (tid == out_tid) store_pending();  // the last pod's outcome
+  // node state back to HBM
+  __syncthreads();
+  for (int i = tid; i < own; i += nt) {
+    const int n = lo + i;
+#pragma unroll
+    for (int r = 0; r < 3; r++) st_ag(&c.requested[(size_t)r * N + n], (int64_t)L.r64[(3 + r) * cap + i]);
+    st_ag(&c.nonzero[n], (int64_t)L.r64[6 * cap + i]);
+    st_ag(&c.nonzero[N + n], (int64_t)L.r64[7 * cap + i]);
+    st_ag(&c.pod_count[n], L.r32[i]);
   }
   handoff_release();
 }

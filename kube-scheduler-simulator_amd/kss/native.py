@@ -80,6 +80,8 @@ SIGNATURES = [
     ("kss_last_geometry", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_kernel", C.c_int, [C.c_void_p]),
     ("kss_last_xcd_local", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("kss_last_shape_table", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("kss_plan_shapes", C.c_int, [C.POINTER(abi.PodSet), C.c_int32, P(C.c_int32), P(C.c_int32)]),
     ("kss_device_go_log", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     ("kss_plan_podset", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.c_void_p]),
     ("kss_plan_podset_ex", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.POINTER(abi.Profile),
@@ -671,6 +673,13 @@ class Context:
         check(lib().kss_last_xcd_local(self.h, out))
         return {"used": out[0], "fallbacks": out[1]}
 
+    def last_shape_table(self) -> Dict[str, int]:
+        """{shapes, rounds} of k_simple's shape table in the last run (kss_last_shape_table);
+        shapes 0: the batch ran without the table."""
+        out = (C.c_int32 * 2)()
+        check(lib().kss_last_shape_table(self.h, out))
+        return {"shapes": out[0], "rounds": out[1]}
+
     def last_kernel(self) -> str:
         k = lib().kss_last_kernel(self.h)
         if k < 0:
@@ -778,6 +787,16 @@ def device_go_log(x, device: int = 0) -> np.ndarray:
     y = np.empty_like(x)
     check(lib().kss_device_go_log(device, x.ctypes.data, y.ctypes.data, len(x)))
     return y
+
+
+def plan_shapes(podset: abi.PodSet, n_scalar: int = 0):
+    """Host-only: (ids, n) -- the resource shape id of every pod as a staged batch numbers them
+    (first appearance order) and the shape count (kss_plan_shapes)."""
+    n_pods = int(podset.n_pods)
+    ids = np.zeros(max(n_pods, 1), dtype=np.int32)
+    n = C.c_int32(0)
+    check(lib().kss_plan_shapes(C.byref(podset), n_scalar, ids.ctypes.data_as(P(C.c_int32)), C.byref(n)))
+    return ids[:n_pods], int(n.value)
 
 
 def plan_podset(cluster: abi.Cluster, podset: abi.PodSet, profile: Optional[abi.Profile] = None) -> dict:

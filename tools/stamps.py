@@ -5,7 +5,8 @@ k_schedule (shard 0, 8 stamps per pod): 0 pod start, 1 plan, 2 filter pass done,
 exchange done, 4 normalize pass done, 5 argmax exchange done, 6 commit + barrier done, 7 the
 spread / inter-pod statistics and their exchange done (inside the filter phase).
 k_simple (every shard, 16 per pod): 0 start, 1 pass B, 2 best-key reduction, 3 pass A,
-4 statistics reduction (= publish), 5 exchange + barrier, 6 commit + ring store.  For
+4 statistics reduction (= publish), 5 exchange + barrier, 6 commit + ring store; with the
+shape table (k_simple_tab) also 12 / 13: waves 1 / 2 finished the refresh.  For
 k_simple the arrival skew of the exchange is reported: per pod, the spread of the
 shards' publish times, and the wait from the LAST publish to each shard's completion
 (propagation + reductions).
@@ -80,6 +81,16 @@ def summarise(path):
             dd = np.median(np.diff(seq, axis=1) / 100.0, axis=0)
             line += (f"\n  red_stats detail (shard 0): wave_red={dd[0]:.2f} write+barrier={dd[1]:.2f}"
                      f" combine={dd[2]:.2f} us")
+        if (s0[ok, 14] == 0).all() and (s0[ok, 12] > 0).any():  # shape table: the refresh of waves 1 (12) and 2 (13)
+            q = s0[ok][(s0[ok, 12] > 0) & (s0[ok, 8] > 0)]
+            end = np.maximum(q[:, 12], q[:, 13])
+            r1 = (q[:, 12] - q[:, 8]) / 100.0
+            slack = (q[:, 5] - end) / 100.0  # stamp 5 follows the closing barrier: what wave 0 still took after the refresh
+            line += (f"\n  shape-table refresh (shard 0): statistics barrier -> wave 1 done median {np.median(r1):.2f} us"
+                     + (f", wave 2 {np.median((q[q[:, 13] > 0, 13] - q[q[:, 13] > 0, 8]) / 100.0):.2f} us"
+                        if (q[:, 13] > 0).any() else "")
+                     + f"; refresh done -> closing barrier passed median {np.median(slack):.2f} us (min {slack.min():.2f},"
+                     f" below 0.10 us in {int((slack < 0.10).sum())}/{len(q)} pods: there the barrier waited for the refresh)")
         if (s0[ok, 14] > 0).any():  # window mode: exchange detail (slots 10-14)
             line += window_detail(s0[ok])
         lines.append(line)
