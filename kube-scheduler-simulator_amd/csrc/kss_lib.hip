@@ -12,7 +12,14 @@
 //                packed into 32-bit static words in HBM (kss_simple.cuh).
 //   k_simple     the sequential loop of those batches (no result record): node rows
 //                in LDS, compact pod records and static words in LDS rings, only the
-//                state-dependent filter / scores per pod, one exchange per pod.
+//                state-dependent filter / scores per pod, one exchange per pod
+//                (simple_schedule: per-wave mode or the two-reduction loop by the
+//                geometry, the window at percentageOfNodesToScore < 100).
+//   k_simple_tab k_simple's per-wave loop with the per-shape score table: the default
+//                profile, no window, no extended resources, at most KSS_MAX_SHAPES
+//                resource shapes; a pod reads its state-dependent values from LDS and
+//                only the waves' candidates are re-evaluated (simple_schedule_tab;
+//                shape_table_ok decides, option shape_table).
 //   k_spread     the sequential loop of batches WITH spread / inter-pod-affinity programs
 //                (no result record): node rows, label ids, the pod's count rows and
 //                the launch's commits in LDS, host-resolved pod programs (GPod),
@@ -305,9 +312,6 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_service(const DevJob* __res
                                  seq, 0u, stamps, smem, xcd);
 }
 
-#ifndef KSS_SIMPLE_PW
-#define KSS_SIMPLE_PW 1  // experiment builds: -DKSS_SIMPLE_PW=0 keeps the two-reduction loop everywhere
-#endif
 // grid = n_jobs * W, as k_schedule; each shard's nodes live in LDS (cap slots).
 // DEF: the profile is the v1.26 default, folded into the code.
 // Pods [k0, min(k1, n_pods)) of every job; the job's stat buffer holds their static words.
@@ -319,33 +323,23 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple(const DevJob* __rest
                                                             unsigned long long* stamps, XPeers X, unsigned epoch0,
                                                             int stat_row0, int k_find) {
   extern __shared__ __attribute__((aligned(16))) long long smem[];
-  const int Wl = X.n > 1 ? X.wl : W;  // shards of this launch (a split grid runs [w_off, w_off + wl))
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
-  int xs = 0;
-  if (X.xcd_local) {  // one cluster, every shard on XCD 0 (xcd_slot); the other workgroups leave
-    if (threadIdx.x == 0)  // the counters behind the granules (and the window's cut granules)
-      H.pad[0] = xcd_slot(reinterpret_cast<int*>(gran + (WIN ? 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 : 2 * (size_t)W * SX_VALS)),
-                          W, (int)gridDim.x, err, X.xcd_local == 2);
-    __syncthreads();
-    xs = H.pad[0];
-    if (xs < 0) return;
-  }
+  const int Wl = X.n > 1 ? X.wl : W;  // shards of this launch (a split grid runs [w_off, w_off + wl))
+  // (an XCD-local grid's counters: behind the granules, and the window's cut granules)
+  auto ctr_off = [&] { return WIN ? 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 : 2 * (size_t)W * SX_VALS; };
+  int xs = 0;  // one cluster, every shard on XCD 0; the other workgroups leave
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, ctr_off, W, err)) < 0) return;
   const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
   const DevJob job = jobs[ji];
   constexpr kss_profile def_prof = default_profile_c();
-  if (!DEF) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&jobs[ji].prof);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&H.prof);
-    for (int i = threadIdx.x; i < (int)(sizeof(kss_profile) / 4); i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-  }
+  if (!DEF) stage_profile(H, jobs[ji].prof);
   const kss_profile& P = DEF ? def_prof : H.prof;
   // per-wave mode when every shard's nodes fit PW_LANES slots per wave (one node per lane)
   const int per = (job.c.N + W - 1) / W, nwave = (int)(blockDim.x >> 6);
   unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;  // (WIN: one job)
   unsigned long long* sp = ji == 0 ? stamps : nullptr;
   const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;  // the chunk's half of a double-buffered table
-  if (per <= PW_LANES * nwave && KSS_SIMPLE_PW)
+  if (per <= PW_LANES * nwave)
     simple_schedule<DEF, true, WIN>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen, job.meta, P,
                                     W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor);
   else
@@ -364,14 +358,8 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab(const DevJob* __
   extern __shared__ __attribute__((aligned(16))) long long smem[];
   const int Wl = X.n > 1 ? X.wl : W;
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
-  int xs = 0;
-  if (X.xcd_local) {  // as k_simple
-    if (threadIdx.x == 0)
-      H.pad[0] = xcd_slot(reinterpret_cast<int*>(gran + 2 * (size_t)W * SX_VALS), W, (int)gridDim.x, err, X.xcd_local == 2);
-    __syncthreads();
-    xs = H.pad[0];
-    if (xs < 0) return;
-  }
+  int xs = 0;  // as k_simple
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return 2 * (size_t)W * SX_VALS; }, W, err)) < 0) return;
   const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
   const DevJob job = jobs[ji];
   unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
@@ -395,16 +383,10 @@ __global__ __launch_bounds__(LB) void k_spread(const DevJob* __restrict__ jobs, 
                                                             int* err, unsigned long long* stamps, int nst, XPeers X,
                                                             unsigned epoch0, HandoffCheck hc, int k_find) {
   extern __shared__ __attribute__((aligned(16))) long long smem[];
-  const int Wl = X.n > 1 ? X.wl : W;
   SpreadHdr& H = *reinterpret_cast<SpreadHdr*>(smem);
-  int xs = 0;
-  if (X.xcd_local) {  // one cluster, every shard on XCD 0 (xcd_slot); the other workgroups leave
-    if (threadIdx.x == 0)
-      H.pad[0] = xcd_slot(reinterpret_cast<int*>(gran + 2 * (size_t)W * gs), W, (int)gridDim.x, err, X.xcd_local == 2);
-    __syncthreads();
-    xs = H.pad[0];
-    if (xs < 0) return;
-  }
+  const int Wl = X.n > 1 ? X.wl : W;
+  int xs = 0;  // one cluster, every shard on XCD 0; the other workgroups leave
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return 2 * (size_t)W * gs; }, W, err)) < 0) return;
   const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
   if (X.tl) {  // the two-level selectHost exchange: the shard's XCD and rank there (tl_register)
     if (threadIdx.x == 0) tl_register(H, X.tl, W, err);
@@ -412,20 +394,7 @@ __global__ __launch_bounds__(LB) void k_spread(const DevJob* __restrict__ jobs, 
   }
   const DevJob job = jobs[ji];
   constexpr kss_profile def_prof = default_profile_c();
-#ifdef KSS_LDS_POISON  // experiment builds: the shard's LDS image filled with a pattern first
-  {
-    const size_t words = spread_lds_bytes(cap, bins_cap, job.c.n_keys, n_res, gq, job.c.n_scalar, FOLD) / 4;
-    uint32_t* p = reinterpret_cast<uint32_t*>(smem);
-    for (size_t i = threadIdx.x; i < words; i += blockDim.x) p[i] = 0x5A5A5A5Au;
-    __syncthreads();
-  }
-#endif
-  if (!DEF) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&jobs[ji].prof);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&H.prof);
-    for (int i = threadIdx.x; i < (int)(sizeof(kss_profile) / 4); i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-  }
+  if (!DEF) stage_profile(H, jobs[ji].prof);
   const kss_profile& P = DEF ? def_prof : H.prof;
   spread_schedule<DEF, FOLD, WIN>(job.trace, job.c, job.gpods, job.stat, job.res_rows, n_res, k0, min(k1, job.n_pods), job.chosen, job.meta, P, W, w,
                   cap, bins_cap, gq, gs, gran ? gran + (size_t)ji * 2 * W * gs : nullptr, X, epoch0, err, stamps, nst, hc,
@@ -2726,7 +2695,7 @@ static bool simple_fits(const Geometry& g, int nsc) {
 // on request (option shape_table = 2).
 static bool shape_table_ok(const Geometry& g, int n_nodes, int n_shapes, const kss_profile& prof, int k_find, int nsc) {
   const int per = (n_nodes + g.W - 1) / std::max(g.W, 1), nwave = g.threads / 64;
-  return (g.W > 1 || opt(O_SHAPE_TABLE) >= 2) && n_shapes >= 1 && n_shapes <= KSS_MAX_SHAPES && k_find == 0 && nsc == 0 && nwave >= 2 && KSS_SIMPLE_PW &&
+  return (g.W > 1 || opt(O_SHAPE_TABLE) >= 2) && n_shapes >= 1 && n_shapes <= KSS_MAX_SHAPES && k_find == 0 && nsc == 0 && nwave >= 2 &&
          per <= PW_LANES * nwave && same_profile(prof, default_profile_c()) &&
          simple_lds_bytes(simple_cap(g), 0, n_shapes) <= KSS_LDS_BUDGET;
 }
@@ -2921,9 +2890,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   return 0;
 }
 
-#ifndef KSS_SPREAD_PREF_THREADS
-#define KSS_SPREAD_PREF_THREADS 512
-#endif
+constexpr int SPREAD_PREF_THREADS = 512;  // k_spread's preferred workgroup: one node per lane up to this many
 
 // k_spread's per-slot LDS arrays are strided by the largest shard's node count (rounded up
 // to 16 slots), not by threads x slots per lane: a 391-node shard of a 100k-node cluster
@@ -3203,11 +3170,11 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   const int n_res = (int)ctx->gneed.res_rows.size();
   bool spread = spread_ok && spread_fits(g, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar);
   if (spread && !simple && opt(O_THREADS) <= 0 && opt(O_FORCE_THREADS) <= 0) {
-    // k_spread: one node per lane where the workgroup allows it (up to KSS_SPREAD_PREF_THREADS):
+    // k_spread: one node per lane where the workgroup allows it (up to SPREAD_PREF_THREADS):
     // its per-node passes are the chain between exchanges (C4: 256 -> 512 lanes, stats +
     // filter + normalise 4.4 -> 2.6 us per pod)
     Geometry g2;
-    if (pick_geometry((int)N, W, KSS_SPREAD_PREF_THREADS, g2) && g2.threads > g.threads &&
+    if (pick_geometry((int)N, W, SPREAD_PREF_THREADS, g2) && g2.threads > g.threads &&
         spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar))
       g = g2;
   }
@@ -3245,7 +3212,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
     Geometry g2;
     if (g.W > 1 && g.W <= xw) {
       xcd_spread = true;
-    } else if (g.W > xw && pick_geometry((int)N, xw, KSS_SPREAD_PREF_THREADS, g2) &&
+    } else if (g.W > xw && pick_geometry((int)N, xw, SPREAD_PREF_THREADS, g2) &&
                spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar)) {
       g = g2;
       xcd_spread = true;

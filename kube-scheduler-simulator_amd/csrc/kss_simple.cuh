@@ -141,6 +141,26 @@ __device__ __forceinline__ int xcd_slot(int* ctr, int W, int grid, int* err, boo
   err_raise(err, 3);
   return -2;
 }
+// The XCD-slot claim at the head of a loop kernel (k_simple, k_simple_tab, k_spread) on an XCD-local
+// grid: thread 0 claims (xcd_slot), the workgroup learns the result through H.pad[0].  ctr_off():
+// where the launch's two counters lie behind its granules, in granules (a callable: the claiming
+// thread alone evaluates it).  Whole workgroup.  Returns xcd_slot's value: the shard, or < 0 (leave).
+template <class Hdr, class CtrOff>
+__device__ __forceinline__ int claim_xcd_shard(Hdr& H, const XPeers& X, unsigned long long* gran, CtrOff ctr_off, int W,
+                                               int* err) {
+  if (threadIdx.x == 0)
+    H.pad[0] = xcd_slot(reinterpret_cast<int*>(gran + ctr_off()), W, (int)gridDim.x, err, X.xcd_local == 2);
+  __syncthreads();
+  return H.pad[0];
+}
+// A runtime (non-default) profile into the header's LDS copy (whole workgroup).
+template <class Hdr>
+__device__ __forceinline__ void stage_profile(Hdr& H, const kss_profile& from) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&from);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&H.prof);
+  for (int i = threadIdx.x; i < (int)(sizeof(kss_profile) / 4); i += blockDim.x) dst[i] = src[i];
+  __syncthreads();
+}
 constexpr int SX_CHUNKS = 2;  // shards swept 64 at a time: W <= 128
 constexpr int STATIC_PODS = 8;  // pods per k_static lane
 constexpr int PF_MAX = 8;       // static words per prefetch lane (host-checked: simple_fits)
@@ -667,6 +687,11 @@ __device__ __forceinline__ long long key_expand(uint32_t k, int kb, int node_bas
   const uint32_t li = m - (k & m);
   return (long long)(((unsigned long long)(k >> kb) << 32) | (0xFFFFFFFFull - ((uint32_t)node_base + li)));
 }
+// The node a selectHost key names (its low word is ~global index), relative to node_base (and to
+// the shard's first node lo: a slot); -1 for key 0, "no feasible node".
+__device__ __forceinline__ int key_node(long long K, int node_base, int lo = 0) {
+  return K ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)K) - node_base - lo : -1;
+}
 __device__ __forceinline__ long long wave_max_key(long long key, int kb, int node_base) {
   if (!kb) return wave_red<OP_MAX>(key);
   uint32_t k = key_compress(key, kb, node_base);
@@ -774,7 +799,7 @@ __device__ __forceinline__ bool simple_exchange(SimpleHdr& H, unsigned long long
   }
   best = wave_max_key(best, kb, node_base);
   // the winner's shard: the one whose row range [s * per, (s + 1) * per) holds it
-  const int gl = best != 0 ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)best) - node_base : -1;
+  const int gl = key_node(best, node_base);
   // {nf, tt, na} of every shard's hypothesis, reduced in one interleaved DPP pass
   uint32_t u[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -793,68 +818,6 @@ __device__ __forceinline__ bool simple_exchange(SimpleHdr& H, unsigned long long
     H.res[2] = u[1];
     H.res[3] = u[2];
   }
-  return true;
-}
-
-// The poll half of simple_exchange for any wave (KSS_PW_ALLPOLL): every shard's row of the
-// exchange at `epoch` (this shard's own row included, published by its wave 0), the winner key
-// and the statistics (the winner's shard contributing its H1), into R of every lane of the
-// calling wave.  False after the wait bound (H.abort set).
-__device__ __forceinline__ bool simple_exchange_poll(SimpleHdr& H, unsigned long long* gran, int W, unsigned epoch,
-                                                     int* err, int per, int node_base, int kb, long long (&R)[4]) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long* base = gran + (size_t)(epoch & 1) * W * SX_VALS;
-  uint32_t got[SX_CHUNKS][SX_VALS];
-  long long best = 0;
-#pragma unroll
-  for (int ch = 0; ch < SX_CHUNKS; ch++) {
-#pragma unroll
-    for (int i = 0; i < SX_VALS; i++) got[ch][i] = 0;
-    if (ch * 64 >= W) continue;
-    const int s = ch * 64 + lane;
-    const bool valid = s < W;
-    long long t0_ = 0;
-    for (unsigned spins = 0;; ++spins) {
-      bool ok = true;
-      unsigned long long g[SX_VALS];
-#pragma unroll
-      for (int i = 0; i < SX_VALS; i++)
-        g[i] = __hip_atomic_load(base + (size_t)(valid ? s : 0) * SX_VALS + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int i = 0; i < SX_VALS; i++) {
-        ok &= !valid || (g[i] >> 32) == epoch;
-        got[ch][i] = valid ? (uint32_t)g[i] : 0u;
-      }
-      if (__all(ok)) break;
-      if (spin_expired(spins, t0_)) {
-        if (lane == 0) {
-          H.abort = 1;
-          err_raise(err, 1);
-        }
-        return false;
-      }
-      spin_pause();
-    }
-    const long long k = (long long)(((unsigned long long)got[ch][1] << 32) | got[ch][0]);
-    best = k > best ? k : best;
-  }
-  best = wave_max_key(best, kb, node_base);
-  const int gl = best != 0 ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)best) - node_base : -1;
-  uint32_t u[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int ch = 0; ch < SX_CHUNKS; ch++) {
-    const int s = ch * 64 + lane;
-    if (s >= W) continue;
-    const bool h1 = gl >= s * per && gl < s * per + per;
-    u[0] += h1 ? got[ch][5] : got[ch][2];
-    u[1] = max(u[1], h1 ? got[ch][6] : got[ch][3]);
-    u[2] = max(u[2], h1 ? got[ch][7] : got[ch][4]);
-  }
-  wave_red_stats(u);
-  R[0] = best;
-  R[1] = u[0];
-  R[2] = u[1];
-  R[3] = u[2];
   return true;
 }
 
@@ -1186,45 +1149,17 @@ __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const 
 }
 
 // AssumePod of pk on shard slot s (LDS node rows; the class / term counts follow after the
-// launch, k_counts).
-// KSS_LANE_COMMIT: the winner's AssumePod over the lanes of one wave (simple_commit_lanes)
-#ifndef KSS_LANE_COMBINE
-#define KSS_LANE_COMBINE 1  // simple_sync_pw: the waves' partials combined lane-parallel (r7d A/B: C2 291.8k -> 301.3k pods/s)
-#endif
-#ifndef KSS_PF_LAST_WAVE
-// per-wave mode with 3+ waves: the last wave (fewest slots) alone prefetches the next records and
-// static words, so the first prefetch wave reaches the statistics barrier with the others (r8u
-// A/B, C2: 303.3 / 303.6 k against 301.6 / 301.5 k pods/s)
-#define KSS_PF_LAST_WAVE 1
-#endif
-#ifndef KSS_PW_ALLPOLL
-// simple_sync_pw: every wave polls the exchange itself, no closing barrier.  r8t A/B: C2 261k
-// against 304k pods/s -- the prefetch waves' polls queue behind their own HBM prefetch loads
-// (vmcnt is in order), so the pod waits for them: off
-#define KSS_PW_ALLPOLL 0
-#endif
-#ifndef KSS_LANE_COMMIT
-#define KSS_LANE_COMMIT 1  // r7c A/B: C2 284.7k -> 290.7k pods/s, C4 unchanged; 0 keeps one lane
-#endif
-static_assert(offsetof(SPod, cnz) == offsetof(SPod, creq) + 3 * sizeof(double), "creq, cnz adjacent");
-// The same AssumePod spread over the lanes of one wave: lane r < 5 adds row 3 + r (Requested cpu /
+// launch, k_counts), spread over the lanes of one wave: lane r < 5 adds row 3 + r (Requested cpu /
 // memory / ephemeral, then NonZeroRequested cpu / memory: creq and cnz are adjacent), lane 5 the
 // pod count, lanes 8.. the extended resources -- the rows' LDS round trips overlap instead of
-// following each other on one lane.
+// following each other on one lane (r7c A/B against one lane adding every row: C2 284.7k ->
+// 290.7k pods/s, C4 unchanged; the one-lane form is retired, DESIGN.md "Retired A/B switches").
+static_assert(offsetof(SPod, cnz) == offsetof(SPod, creq) + 3 * sizeof(double), "creq, cnz adjacent");
 __device__ __forceinline__ void simple_commit_lanes(const SimpleShard& L, const SPod& pk, int s, int lane) {
   const int cap = L.cap;
   if (lane < 5) L.r64[(3 + lane) * cap + s] += (&pk.creq[0])[lane];
   if (lane == 5) L.r32[s] += 1;
   if (lane >= 8 && lane < 8 + L.nsc) L.sc[(size_t)(L.nsc + lane - 8) * cap + s] += pk.sc_req[lane - 8];
-}
-__device__ __forceinline__ void simple_commit_slot(const SimpleShard& L, const SPod& pk, int s) {
-  const int cap = L.cap;
-#pragma unroll
-  for (int r = 0; r < 3; r++) L.r64[(3 + r) * cap + s] += pk.creq[r];
-  L.r64[6 * cap + s] += pk.cnz[0];
-  L.r64[7 * cap + s] += pk.cnz[1];
-  L.r32[s] += 1;
-  for (int i = 0; i < L.nsc; i++) L.sc[(size_t)(L.nsc + i) * cap + s] += pk.sc_req[i];
 }
 
 // Per-wave mode's one reduction per pod: the waves' best keys and H0 / H1 statistics in one
@@ -1234,6 +1169,10 @@ __device__ __forceinline__ void simple_commit_slot(const SimpleShard& L, const S
 // R = {winner key, nf, max TT, max NA of the next pod}.  False if the launch aborted.
 // `idle` runs on every wave right after the statistics barrier: the waves other than wave 0
 // wait out the exchange there (the prefetch loads are issued from it).
+// Wave 0 alone polls the exchange and a closing barrier hands the result to the others.  Every
+// wave polling for itself, with no closing barrier, lost (r8t A/B: C2 261k against 304k pods/s):
+// the prefetch waves' polls queue behind their own HBM prefetch loads (vmcnt is in order), so
+// the pod waits for them.  (Retired: DESIGN.md "Retired A/B switches".)
 template <typename Idle>
 __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long long wbest, uint32_t (&u)[6], int W,
                                                int w, unsigned epoch, unsigned long long* gran, const XPeers& X,
@@ -1253,10 +1192,10 @@ __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long l
   if (sp && threadIdx.x == 0) sp[8] = wall_clock64();
   idle();
   if (wave == 0) {  // wave 0 alone combines (every lane the same few LDS words: broadcasts) and exchanges
-#if KSS_LANE_COMBINE
     // lane v < nw reads wave v's partials (one LDS round trip for all waves), then three DPP
     // steps over the (at most 8) lanes: the largest key, and the six statistics with the best
-    // wave contributing its H1
+    // wave contributing its H1 (r7d A/B against every lane reading the waves' rows in turn: C2
+    // 291.8k -> 301.3k pods/s)
     const bool in = lane < nw;
     const long long* hv = H.red[parity][in ? lane : 0];
     const long long kv = in ? hv[0] : 0;
@@ -1279,49 +1218,6 @@ __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long l
     dpp_stats_step<0x141, 0xF>(t);
 #pragma unroll
     for (int i = 0; i < 6; i++) t[i] = (uint32_t)__builtin_amdgcn_readlane((int)t[i], 0);
-#else
-    // waves 0 and 1 (the usual per-wave geometry) read at once, unconditionally; waves 2.. in a loop
-    const long long* h0 = H.red[parity][0];
-    const long long* h1 = H.red[parity][nw > 1 ? 1 : 0];
-    long long a0[7], a1[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-      a0[i] = h0[i];
-      a1[i] = h1[i];
-    }
-    if (nw < 2) a1[0] = 0;
-    // the wave holding the shard's best (keys carry the node index: one wave at most)
-    long long best = a0[0];
-    int ws = best ? 0 : -1;
-    if (a1[0] > best) {
-      best = a1[0];
-      ws = 1;
-    }
-    for (int v = 2; v < nw; v++) {
-      const long long b = H.red[parity][v][0];
-      ws = b > best ? v : ws;
-      best = b > best ? b : best;
-    }
-    // the best wave contributes its H1, the others their H0
-    const bool w0 = ws == 0, w1 = ws == 1;
-    uint32_t t[6];
-    t[0] = (uint32_t)a0[1] + (nw > 1 ? (uint32_t)a1[1] : 0u);
-    t[1] = max((uint32_t)a0[2], nw > 1 ? (uint32_t)a1[2] : 0u);
-    t[2] = max((uint32_t)a0[3], nw > 1 ? (uint32_t)a1[3] : 0u);
-    t[3] = (uint32_t)(w0 ? a0[4] : a0[1]) + (nw > 1 ? (uint32_t)(w1 ? a1[4] : a1[1]) : 0u);
-    t[4] = max((uint32_t)(w0 ? a0[5] : a0[2]), nw > 1 ? (uint32_t)(w1 ? a1[5] : a1[2]) : 0u);
-    t[5] = max((uint32_t)(w0 ? a0[6] : a0[3]), nw > 1 ? (uint32_t)(w1 ? a1[6] : a1[3]) : 0u);
-    for (int v = 2; v < nw; v++) {
-      const long long* h = H.red[parity][v];
-      const int o = v == ws ? 4 : 1;
-      t[0] += (uint32_t)h[1];
-      t[1] = max(t[1], (uint32_t)h[2]);
-      t[2] = max(t[2], (uint32_t)h[3]);
-      t[3] += (uint32_t)h[o];
-      t[4] = max(t[4], (uint32_t)h[o + 1]);
-      t[5] = max(t[5], (uint32_t)h[o + 2]);
-    }
-#endif
     if (sp && lane == 0) sp[4] = wall_clock64();
     if (W == 1) {  // the winner (if any) is this shard's best
       const bool h1 = best != 0;
@@ -1331,42 +1227,16 @@ __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long l
         H.res[1] = h1 ? t[3] : t[0];
         H.res[2] = h1 ? t[4] : t[1];
         H.res[3] = h1 ? t[5] : t[2];
-        if (!KSS_LANE_COMMIT && commit && h1) simple_commit_slot(L, pk, slot);
       }
-      if (KSS_LANE_COMMIT && commit && h1) simple_commit_lanes(L, pk, slot, lane);
-    } else if (KSS_PW_ALLPOLL) {  // publish only: every wave polls below
-      if (lane < SX_VALS) {
-        const unsigned long long key = (unsigned long long)best, tag = (unsigned long long)epoch << 32;
-        uint32_t x = (uint32_t)key;
-        x = lane == 1 ? (uint32_t)(key >> 32) : x;
-#pragma unroll
-        for (int i = 0; i < 6; i++) x = lane == i + 2 ? t[i] : x;
-        xpub(X, gran, ((size_t)(epoch & 1) * W + w) * SX_VALS + lane, tag | x);
-      }
+      if (commit && h1) simple_commit_lanes(L, pk, slot, lane);
     } else {
       const long long v[7] = {best, t[0], t[1], t[2], t[3], t[4], t[5]};
-      if (simple_exchange(H, gran, X, W, w, epoch, err, v, per, node_base, kb) && commit && (KSS_LANE_COMMIT || lane == 0)) {
+      if (simple_exchange(H, gran, X, W, w, epoch, err, v, per, node_base, kb) && commit) {
         const long long K = H.res[0];  // (written by lane 0 of this wave: in order)
-        const int x = K ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)K) - node_base - lo : -1;
-        if (x >= 0 && x < own) {
-          if (KSS_LANE_COMMIT) simple_commit_lanes(L, pk, x, lane);
-          else simple_commit_slot(L, pk, x);
-        }
+        const int x = key_node(K, node_base, lo);
+        if (x >= 0 && x < own) simple_commit_lanes(L, pk, x, lane);
       }
     }
-  }
-  if (KSS_PW_ALLPOLL && W > 1) {
-    // every wave polls the shards' rows itself and commits pod k on the winner's slot if that slot
-    // is one of its own: no closing barrier.  Each wave's next reads (pass B / pass A) touch only
-    // its own slots, and a wave reaching the next statistics barrier has finished this pod's poll,
-    // so the reduction rows (parity-alternated) are never overwritten while read.
-    parity ^= 1;
-    if (!simple_exchange_poll(H, gran, W, epoch, err, per, node_base, kb, R)) return false;
-    const long long K = R[0];
-    const int x = K ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)K) - node_base - lo : -1;
-    const int pwv = (own + nw - 1) / nw;  // the wave's slots (simple_schedule's per-wave split)
-    if (commit && x >= 0 && x < own && x / max(pwv, 1) == wave) simple_commit_lanes(L, pk, x, lane);
-    return true;
   }
   parity ^= 1;
   lds_barrier();
@@ -1774,7 +1644,7 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
     }
     if (sp && lane == 0) sp[10] = wall_clock64();
     if (ok) {
-      const int gl = gbest != 0 ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)gbest) - node_base : -1;
+      const int gl = key_node(gbest, node_base);
       // each lane's shard: H1 when the winner is one of its nodes
       uint32_t Fa[SX_CHUNKS], Fb[SX_CHUNKS], ta[SX_CHUNKS], tb[SX_CHUNKS], na_[SX_CHUNKS], nb_[SX_CHUNKS];
       uint32_t A = 0, B = 0, sa[SX_CHUNKS], sb[SX_CHUNKS], TA[SX_CHUNKS], TB[SX_CHUNKS];
@@ -1875,7 +1745,7 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
     nf = k_find;
     const bool need = H.win[10] != 0;
     const long long best = H.res[0];
-    const int gl = best != 0 ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)best) - node_base : -1;
+    const int gl = key_node(best, node_base);
     const bool won = gl >= lo && gl < lo + own;
     const int sub_s = won ? gl - lo : -1;
     const int sub_h = PW ? L.cap + (won ? (gl - lo) / max(pwv, 1) : 0) : L.cap;
@@ -2019,9 +1889,11 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
   const int lane = tid & 63, wv = tid >> 6;
   const int pwv = (own + nwave - 1) / nwave;  // per-wave mode: the wave's node slots (<= PW_LANES)
   const int kb = key_bits(prof, c.N);  // 32-bit key reductions when the keys fit (0: 64-bit)
-  // prefetch lanes: every wave but wave 0 (readfirstlane: a wave-uniform, scalar branch)
-  // (KSS_PF_LAST_WAVE, per-wave mode with 3+ waves: the last wave alone prefetches -- A/B)
-  const int pf_w0 = (PW && KSS_PF_LAST_WAVE && nwave >= 3) ? nwave - 1 : 1;
+  // prefetch lanes: every wave but wave 0 (readfirstlane: a wave-uniform, scalar branch).
+  // Per-wave mode with 3+ waves: the last wave (fewest slots) alone prefetches, so the first
+  // prefetch wave reaches the statistics barrier with the others (r8u A/B, C2: 303.3 / 303.6 k
+  // against 301.6 / 301.5 k pods/s)
+  const int pf_w0 = (PW && nwave >= 3) ? nwave - 1 : 1;
   const bool pf_wave = nwave == 1 || __builtin_amdgcn_readfirstlane(tid >> 6) >= pf_w0;
   uint4 pfq = make_uint4(0, 0, 0, 0);  // prefetched record / static words of pod k+PD, live across the loop
   uint32_t pfw[PF_MAX];
@@ -2178,10 +2050,7 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       const bool won = x >= lo && x < hi;
       sub_s = won ? x - lo : -1;
       sub_h = PW ? cap + (won ? (x - lo) / max(pwv, 1) : 0) : cap;
-      if (!PW && !WIN && won && (KSS_LANE_COMMIT ? tid < 64 : tid == 0)) {
-        if (KSS_LANE_COMMIT) simple_commit_lanes(L, pk, x - lo, tid);
-        else simple_commit_slot(L, pk, x - lo);
-      }
+      if (!PW && !WIN && won && tid < 64) simple_commit_lanes(L, pk, x - lo, tid);
       // the HBM-only class / term counts are applied after the launch (k_counts): nothing in
       // this loop reads them
     }
@@ -2243,7 +2112,10 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
 // of a pod, and written (the commit) between the closing barrier and the next statistics
 // barrier; pnd is written in the first interval and read in the second.  (So the commit is not
 // wave 0's, before the closing barrier, as in simple_sync_pw's own: commit = false there.)
-static_assert(!KSS_PW_ALLPOLL, "the shape table rests on simple_sync_pw's closing barrier");
+// The shard load / write-back, pending outcome and prefetch below restate simple_schedule's.
+// Sharing them as inline helpers changed the code of all five loop kernels (more SGPR spill
+// traffic) and cost C1 8.6 %, pct 0 0.9 %, C2 0.3 %: profiles/r10b_loop_pieces_ab.txt.  A change
+// to one of these pieces is made in both loops.
 __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __restrict__ spods,
                                                     const uint32_t* __restrict__ stat, int k0, int k1, int n_pods,
                                                     int32_t* chosen, PodMeta* meta, int W, int w, int cap,
@@ -2335,7 +2207,7 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
   unsigned epoch = epoch0;
   const int kb = key_bits(prof, c.N);
   // prefetch lanes as in simple_schedule
-  const int pf_w0 = (KSS_PF_LAST_WAVE && nwave >= 3) ? nwave - 1 : 1;
+  const int pf_w0 = nwave >= 3 ? nwave - 1 : 1;
   const bool pf_wave = __builtin_amdgcn_readfirstlane(tid >> 6) >= pf_w0;
   uint4 pfq = make_uint4(0, 0, 0, 0);
   uint32_t pfw[PF_MAX];

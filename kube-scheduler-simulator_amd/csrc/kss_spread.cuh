@@ -327,19 +327,9 @@ __device__ __forceinline__ void wave_red32(int32_t (&v)[K], const int (&ops)[K])
 // also count in lgkmcnt and make every following LDS wait on the HBM stores.
 // phase bit 0: publish (wave 0), bit 1: sweep by wave gw of nsw sweeping waves (lanes of
 // every sweeping wave share the values: T = 64 nsw / M lanes per value).
-#ifndef KSS_LANE_RED
-#define KSS_LANE_RED 0  // spread_reduce: the waves' partials written by K lanes (r7g A/B: C4 -0.5 %, C3 -1.4 %: off)
-#endif
 constexpr int G_XS = 16;  // at most this many shards polled per lane at once (4 / 8 / 16 by need)
-#ifndef KSS_SPREAD_SAFE
-#define KSS_SPREAD_SAFE 0  // experiment builds: extra barriers around the exchanges
-#endif
-#ifndef KSS_SPREAD_SWEEP_WAVES
-#define KSS_SPREAD_SWEEP_WAVES 4  // at most this many waves sweep one exchange (512-lane shards: half)
-#endif
-#ifndef KSS_SPREAD_MW_MIN
-#define KSS_SPREAD_MW_MIN (64 * 4)  // W x values above which every wave sweeps a share (C3: 40 x 13)
-#endif
+constexpr int SPREAD_SWEEP_WAVES = 4;  // at most this many waves sweep one exchange (512-lane shards: half)
+constexpr int SPREAD_MW_MIN = 64 * 4;  // W x values above which every wave sweeps a share (C3: 40 x 13)
 __device__ __forceinline__ bool spread_exchange(SpreadHdr& H, int32_t* xs, unsigned long long* gran_, const XPeers& X,
                                                 int W, int wself, int gs,
                                                 unsigned epoch, int* err, int K, unsigned opbits, int sum_lo, int ns,
@@ -795,14 +785,9 @@ __device__ __forceinline__ bool spread_reduce(SpreadHdr& H, int32_t* xs, int W, 
 #pragma unroll
   for (int k = 0; k < K; k++) r[k] = v[k];
   wave_red32(r, ops);
-  if (KSS_LANE_RED) {  // lane k writes value k: one LDS store instruction instead of K on lane 0
-    if (lane < K) {
-      int32_t x = r[0];
-#pragma unroll
-      for (int k = 1; k < K; k++) x = lane == k ? r[k] : x;
-      H.red[wave][lane] = x;
-    }
-  } else if (lane == 0) {
+  // lane 0 writes the K partials (lane k writing value k, one LDS store instruction instead of K,
+  // lost: r7g A/B, C4 -0.5 %, C3 -1.4 %)
+  if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < K; k++) H.red[wave][k] = r[k];
   }
@@ -843,7 +828,7 @@ __device__ __forceinline__ bool spread_reduce(SpreadHdr& H, int32_t* xs, int W, 
       if (sp && threadIdx.x == 0) sp[4] = wall_clock64();
       lds_barrier();
       if (H.abort) return false;
-    } else if (nw == 1 || (long long)W * M <= (long long)KSS_SPREAD_MW_MIN) {  // one polling round for one wave: wave 0 alone
+    } else if (nw == 1 || (long long)W * M <= (long long)SPREAD_MW_MIN) {  // one polling round for one wave: wave 0 alone
       if (wave == 0 && spread_exchange(H, xs, gran, X, W, w, gs, epoch, err, KX, opbits, sum_lo, ns, or_lo, no, sp, 0, 1, 3,
                                        0, or2_lo, no2) &&
           minima_q)
@@ -855,7 +840,7 @@ __device__ __forceinline__ bool spread_reduce(SpreadHdr& H, int32_t* xs, int W, 
       if (wave == 0)
         spread_exchange(H, xs, gran, X, W, w, gs, epoch, err, KX, opbits, sum_lo, ns, or_lo, no, sp, 0, 1, 1, 0, or2_lo, no2);
       lds_barrier();  // the slots hold the operators' identities before any wave folds into them
-      const int nsw = min(nw, KSS_SPREAD_SWEEP_WAVES);  // the sweeping waves (the rest wait)
+      const int nsw = min(nw, SPREAD_SWEEP_WAVES);  // the sweeping waves (the rest wait)
       if (wave < nsw)
         spread_exchange(H, xs, gran, X, W, w, gs, epoch, err, KX, opbits, sum_lo, ns, or_lo, no, nullptr, wave, nsw, 2, 0,
                         or2_lo, no2);
@@ -870,7 +855,6 @@ __device__ __forceinline__ bool spread_reduce(SpreadHdr& H, int32_t* xs, int W, 
   for (int k = 0; k < K; k++) v[k] = xs[k];  // (k >= kx: the identity, or the folded minimum)
   // no barrier here: the next reduction rewrites xs[0..K) (publish resets, or the local
   // path's stores) only behind its own first barrier, which every wave reaches after reading
-  if (KSS_SPREAD_SAFE) lds_barrier();  // experiment: a trailing barrier after every exchange
   return true;
 }
 
@@ -909,7 +893,7 @@ __device__ __forceinline__ bool spread_argmax(SpreadHdr& H, int W, int w, int gs
            tag | (kb ? kc : (lane ? (uint32_t)((unsigned long long)best >> 32) : (uint32_t)best)));
     KSS_GLOBAL const unsigned long long* base = gp(gran) + (size_t)(epoch & 1) * W * gs;
     long long m = 0;
-    const int nsw = min(nw, KSS_SPREAD_SWEEP_WAVES);  // the polling waves (the rest add 0)
+    const int nsw = min(nw, SPREAD_SWEEP_WAVES);  // the polling waves (the rest add 0)
     const int stride = 64 * nsw;
     for (int c0 = wave * 64; wave < nsw && c0 < W; c0 += 4 * stride) {
       unsigned long long lo[4], hi[4];
@@ -1159,12 +1143,12 @@ __device__ __forceinline__ bool spread_argmax_pay(SpreadHdr& H, const SpreadShar
       if (tl_argmax_pay(H, X, W, epoch, key_compress(best, kb, node_base), np, err, m) && lane == 0)
         xs[0] = (int32_t)(m ^ 0x80000000u);
     }
-  } else if (nw == 1 || (long long)W * M <= (long long)KSS_SPREAD_MW_MIN) {
+  } else if (nw == 1 || (long long)W * M <= (long long)SPREAD_MW_MIN) {
     if (wave == 0) spread_exchange(H, xs, gran, X, W, w, gs, epoch, err, K, opbits, 0, 0, 0, 0, nullptr, 0, 1, 3, np);
   } else {
     if (wave == 0) spread_exchange(H, xs, gran, X, W, w, gs, epoch, err, K, opbits, 0, 0, 0, 0, nullptr, 0, 1, 1, np);
     lds_barrier();  // identities in the slots before any wave folds into them
-    const int nsw = min(nw, KSS_SPREAD_SWEEP_WAVES);
+    const int nsw = min(nw, SPREAD_SWEEP_WAVES);
     if (wave < nsw) spread_exchange(H, xs, gran, X, W, w, gs, epoch, err, K, opbits, 0, 0, 0, 0, nullptr, wave, nsw, 2, np);
   }
   lds_barrier();
@@ -1749,7 +1733,6 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
     int32_t* tw = tr.words + ((size_t)k * W + w) * G_TW;
 #endif
     // ---- stats: PodTopologySpread PreFilter, InterPodAffinity PreFilter / PreScore ----
-    if (KSS_SPREAD_SAFE) lds_barrier();
     if (FOLD && evaluated && folded) {  // the bins already hold the cluster statistics
 #pragma unroll
       for (int i = 0; i < MAXH; i++) hard_min[i] = i < q.n_hard ? H.fmin[i] : INT32_MAX;
@@ -2318,7 +2301,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       }
     }
 #endif
-    if (KSS_LANE_COMMIT && won && tid < 64) {  // the rows over wave 0's lanes (simple_commit_lanes)
+    if (won && tid < 64) {  // the rows over wave 0's lanes (simple_commit_lanes)
       const int s = x - lo;
       const SPod& pk = q.dyn;
       if (tid < 5) L.r64[(3 + tid) * cap + s] += (&pk.creq[0])[tid];
@@ -2327,18 +2310,6 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       if (tid == 32)
         for (int i = 0; i < q.n_cmt; i++)
           if (q.cmt[i] >= 0) L.cnt[q.cmt[i] * cap + s] += 1;
-    }
-    if (!KSS_LANE_COMMIT && won && tid == 0) {
-      const int s = x - lo;
-      const SPod& pk = q.dyn;
-#pragma unroll
-      for (int r = 0; r < 3; r++) L.r64[(3 + r) * cap + s] += pk.creq[r];
-      L.r64[6 * cap + s] += pk.cnz[0];
-      L.r64[7 * cap + s] += pk.cnz[1];
-      L.r32[s] += 1;
-      for (int i = 0; i < nsc; i++) L.sc[(size_t)(nsc + i) * cap + s] += pk.sc_req[i];
-      for (int i = 0; i < q.n_cmt; i++)
-        if (q.cmt[i] >= 0) L.cnt[q.cmt[i] * cap + s] += 1;
     }
     // ---- prefetched data of pods k+1 / k+2 -> their LDS slots ----
     if (pf_on && k + 2 < k1) {  // lanes past the end rewrite the last uint4 with its own value

@@ -265,3 +265,73 @@ def test_batches_that_do_not_take_the_table(why):
     if why == "custom_profile":
         prof = _custom_profile()
     _run(nodes, bound, pods, {"shards": 3, "force_threads": 128}, 0, prof=prof, kernel=None)
+
+
+# The loop variants of kss_simple.cuh at their smallest shapes.  k_simple picks per-wave mode by its
+# own rule, per <= 63 x waves (per: the nodes of a full shard); the geometry options pin shards and
+# lanes, so the rule places each case.  (nodes, shards, pods, profile, pct, extended resources,
+# shape_table option, loop)
+VARIANTS = {
+    "per_wave_full_waves": (378, 3, 200, "default", 100, 0, 0, "per-wave"),
+    "per_wave_short_last_shard": (377, 3, 200, "custom", 100, 1, 0, "per-wave"),
+    "per_wave_window": (378, 3, 200, "default", 30, 0, 0, "per-wave"),
+    "two_reduction_default": (127, 1, 200, "default", 100, 1, 0, "two-reduction"),
+    "two_reduction_custom": (127, 1, 200, "custom", 100, 1, 0, "two-reduction"),
+    "two_reduction_window": (127, 1, 200, "default", 30, 0, 0, "two-reduction"),
+    "table": (378, 3, 200, "default", 100, 0, 1, "table"),
+    "table_one_pod": (378, 3, 1, "default", 100, 0, 1, "table"),
+    "table_three_pods": (378, 3, 3, "default", 100, 0, 1, "table"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(VARIANTS))
+def test_loop_variants_at_their_smallest_shapes(case):
+    """simple_schedule in per-wave mode (two waves of 63 slots each: 126 nodes per shard, the last
+    shard full or one node short), its two-reduction form (127 nodes on one shard of 128 lanes, one
+    node past per-wave mode's limit), both with the window (pct 30: numFeasibleNodesToFind is 113 of
+    378 nodes and the 100-node floor of 127, so the window cuts), with an extended resource and a custom
+    profile, and simple_schedule_tab, also on batches of one pod (the prologue and one iteration)
+    and of three (the prefetch distance: nothing is prefetched).  Chosen nodes, per-pod outcomes and
+    the final node state against the C oracle; the routing through last_kernel, last_geometry,
+    last_shape_table and the kernel's rule for per-wave mode."""
+    n_nodes, shards, n_pods, profile, pct, n_ext, table, loop = VARIANTS[case]
+    if n_ext:
+        nodes, bound, pods = progfuzz.make(90 + n_nodes, n_nodes, n_pods, n_extended=n_ext, programs=False)
+    else:
+        nodes, bound, pods = _manifests(90 + n_nodes, n_nodes, n_pods, BASE_SHAPES)
+    prof = _custom_profile() if profile == "custom" else abi.default_profile()
+    prof.pct_nodes_to_score = pct
+    if pct < 100:  # k_simple runs the window for pods without a PreFilterResult node list (metadata.name terms)
+        for p in pods:
+            na = p["spec"].get("affinity", {}).get("nodeAffinity", {})
+            req = na.get("requiredDuringSchedulingIgnoredDuringExecution", {})
+            if any("matchFields" in t for t in req.get("nodeSelectorTerms", [])):
+                del na["requiredDuringSchedulingIgnoredDuringExecution"]
+    cc, cp, _ = compile_cluster(nodes, bound, pods)
+    assert len(cc.scalars) == n_ext
+    want = oracle_c.schedule(prof, cc.as_struct(), cp.as_struct(), cp.n, cc.n_nodes, record="meta",
+                             n_classes=len(cc.classes), n_terms=len(cc.terms))
+    if pct < 100:  # the window cuts: pods keep exactly numFeasibleNodesToFind nodes of more, none keeps more
+        k_find = max(100, n_nodes * pct // 100)  # 100 (the floor) of 127 nodes, 113 of 378
+        kept = [want[1].meta(j)["n_feasible"] for j in range(n_pods)]
+        assert k_find < n_nodes and max(kept) == k_find and kept.count(k_find) > 1
+    _, n_shapes = native.plan_shapes(cp.as_struct(), n_ext)
+    native.reset_options()
+    native.set_option("shards", shards)
+    native.set_option("force_threads", 128)
+    native.set_option("shape_table", table)
+    ctx = native.Context(prof)
+    ctx.load(cc.as_struct())
+    chosen = ctx.schedule_batch(cp.as_struct(), cp.n)
+    assert ctx.last_kernel() == "k_simple"
+    g = ctx.last_geometry()
+    assert (g["shards"], g["threads"]) == (shards, 128), g
+    per = -(-n_nodes // shards)
+    assert (per <= 63 * (g["threads"] // 64)) == (loop != "two-reduction")
+    if loop == "table":
+        assert 1 <= n_shapes <= 64
+        assert ctx.last_shape_table() == {"shapes": n_shapes, "rounds": _rounds(128, n_shapes)}
+    else:
+        assert ctx.last_shape_table() == {"shapes": 0, "rounds": 0}
+    _check(ctx, chosen, cc, cp.n, want)
+    ctx.close()
