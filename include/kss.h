@@ -785,6 +785,13 @@ int kss_last_xcd_local(kss_ctx* ctx, int32_t* out2);
  * pod.  Option "shape_table": 1 (default) grids of two or more shards, 2 also a single shard (no
  * exchange hides the re-evaluation there: slower, for tests), 0 never. */
 int kss_last_shape_table(kss_ctx* ctx, int32_t* out2);
+/* The shape-table loop's cross-shard exchange in the last run: out2[0] = 1 when it ran the flat
+ * form, out2[1] = its entries (shards x waves; 0 otherwise).  Flat: every wave of every shard
+ * publishes its own best key and statistics and one sweep per shard reduces all of them, in
+ * place of a reduction inside each shard followed by one over the shards (same results).  Taken
+ * by a shape-table batch on two or more shards of one part (not a split grid) with at most 128
+ * entries.  Option "flat_exchange": 1 (default) where admitted, 0 the two-level form. */
+int kss_last_simple_exchange(kss_ctx* ctx, int32_t* out2);
 /* kernel of the last scheduling launch: 0 general (k_schedule), 1 compact (k_simple:
  * batches without spread / inter-pod programs and without a record), 2 k_spread (batches
  * with programs, without a record), 3 k_preempt (kss_postfilter_pod); <0 on error */

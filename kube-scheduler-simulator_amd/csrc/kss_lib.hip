@@ -20,7 +20,11 @@
 //                resource shapes; a pod reads its state-dependent values from LDS and
 //                only the waves' candidates are re-evaluated (simple_schedule_tab;
 //                shape_table_ok decides, option shape_table).
-//   k_spread     the sequential loop of batches WITH spread / inter-pod-affinity programs
+//   k_simple_tab_flat  k_simple_tab with the flat exchange: every wave publishes its own key
+//                and statistics, one sweep over shards x waves entries replaces the in-shard
+//                reduction followed by the cross-shard one (simple_sync_flat;
+//                flat_exchange_ok decides, option flat_exchange).
+//   k_spread    the sequential loop of batches WITH spread / inter-pod-affinity programs
 //                (no result record): node rows, label ids, the pod's count rows and
 //                the launch's commits in LDS, host-resolved pod programs (GPod),
 //                32-bit exchanges (kss_spread.cuh).
@@ -72,7 +76,8 @@ enum KssOpt {
   O_SHARDS, O_XCD, O_XCD_SHARDS, O_NO_SIMPLE, O_NO_SPREAD, O_AXIS_BLOCKS, O_AXIS_NO_FOLD, O_NODES_PER_SHARD,
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
-  O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE, O_N
+  O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
+  O_FLAT_EXCHANGE, O_N
 };
 struct OptDef {
   const char* name;
@@ -109,6 +114,7 @@ const OptDef kOptDefs[O_N] = {
     {"spread_two_level", "KSS_SPREAD_TWO_LEVEL", 1},      // k_spread at W > 64: 1 two-level selectHost exchange, 2 + reductions
     {"spread_lb256", "KSS_SPREAD_LB256", 1},              // k_spread compiled for <= 256 lanes when the shard fits
     {"shape_table", "KSS_SHAPE_TABLE", 1},                // k_simple's shape table: 1 sharded grids that admit it, 2 also one shard, 0 never
+    {"flat_exchange", "KSS_FLAT_EXCHANGE", 1},            // the shape-table loop's exchange: 1 every wave publishes (one sweep), 0 two-level
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -364,9 +370,15 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab(const DevJob* __
   const DevJob job = jobs[ji];
   unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
   const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
-  simple_schedule_tab(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w, cap, g, X,
-                      epoch0, err, ji == 0 ? stamps : nullptr, smem, n_shapes);
+  simple_schedule_tab<false>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w, cap, g,
+                             X, epoch0, err, ji == 0 ? stamps : nullptr, smem, n_shapes);
 }
+
+// k_simple_tab with the flat exchange (simple_sync_flat); defined at the end of this file, behind
+// every other kernel.
+__global__ void k_simple_tab_flat(const DevJob* __restrict__ jobs, kss_profile prof, int W, int cap, int k0, int k1,
+                                  unsigned long long* gran, int* err, unsigned long long* stamps, XPeers X,
+                                  unsigned epoch0, int stat_row0, int n_shapes);
 
 // grid = W (one cluster); each shard's nodes live in LDS (cap slots); bins_cap: histogram +
 // presence values of the exchange vector.  DEF: the v1.26 default profile, folded.  FOLD: the
@@ -776,6 +788,7 @@ struct kss_ctx {
   int xcd_w = 0;              // KSS_XCD_SHARDS: shards of an XCD-local grid (tuning; default: CUs per XCD)
   int last_xcd[2] = {0, 0};   // the last run: XCD-local grid used, chunks that fell back to an unrestricted grid
   int spod_shapes = 0;        // resource shapes of the staged pods (build_spods)
+  int last_flat[2] = {0, 0};   // the last run: the table loop's flat exchange used, its entries (shards x waves)
   int last_shape[2] = {0, 0};  // the last run: shapes in k_simple's table (0: not used), rounds per refresh
   int nodes_per_shard = 128;  // KSS_NODES_PER_SHARD (C2 sweep: 128 > 256 > 512 nodes per shard)
   int pref_threads = 256;     // KSS_THREADS
@@ -2700,6 +2713,21 @@ static bool shape_table_ok(const Geometry& g, int n_nodes, int n_shapes, const k
          simple_lds_bytes(simple_cap(g), 0, n_shapes) <= KSS_LDS_BUDGET;
 }
 
+// The table loop's flat exchange (k_simple_tab_flat, simple_sync_flat) on geometry g, for a batch
+// that shape_table_ok admits: two or more shards on one part (a split grid's peers exchange per
+// shard), at most SXF_MAX_E wave entries, and selectHost keys that compress to 32 bits (key_bits
+// of kss_simple.cuh: 2^kb > N and every total below 2^(32 - kb); the default profile's totals are
+// at most 1300, so every N k_simple admits passes).  Otherwise the two-level form runs.
+static bool flat_exchange_ok(const Geometry& g, int n_nodes, const kss_profile& prof, bool split_grid) {
+  long long tmax = 0;
+  for (int p = 0; p < KSS_NSCORE; p++)
+    if ((prof.score_enabled >> p) & 1u) tmax += 100ll * std::max(prof.weight[p], 0);
+  int kb = 0;
+  while (kb < 32 && (1ll << kb) <= (long long)std::max(n_nodes, 1)) kb++;
+  const bool key32 = kb < 32 && tmax < (1ll << (32 - kb));
+  return opt(O_FLAT_EXCHANGE) && g.W > 1 && !split_grid && g.W * (g.threads / 64) <= SXF_MAX_E && key32;
+}
+
 // Extended (scalar) resources on k_simple / k_spread: their NodeResourcesFit filter and
 // AssumePod run in LDS; a profile that scores one (fit / BalancedAllocation resources past
 // ephemeral-storage) keeps the batch on k_schedule.
@@ -2792,7 +2820,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          unsigned long long* stamps = nullptr, hipEvent_t* ev = nullptr, const SplitRun* split = nullptr,
                          int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
                          hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
-                         int n_shapes = 0) {
+                         int n_shapes = 0, bool flat = false) {
   // st2 (with pev, two events per chunk): the static words of chunk i+1 are computed on st2 into the
   // other half of a double-buffered table while k_simple runs chunk i on st (each job's table holds
   // 2 x chunk rows); k_simple of chunk i waits for its k_static, k_static of chunk i+1 for
@@ -2804,7 +2832,13 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
   const bool tab = n_shapes > 0 && def && !win && nsc == 0;
   const size_t shmem = simple_lds_bytes(cap, nsc, tab ? n_shapes : 0);
-  const void* fn = tab   ? (const void*)k_simple_tab
+  // flat: the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
+  flat = flat && tab && n_jobs == 1 && !(split && split->X.n > 1);
+  // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
+  if (flat && gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
+    return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
+  const void* fn = flat  ? (const void*)k_simple_tab_flat
+                   : tab ? (const void*)k_simple_tab
                    : win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
                          : (def ? (const void*)k_simple<true, false> : (const void*)k_simple<false, false>);
   int last_arg = tab ? n_shapes : k_find;  // k_simple_tab: n_shapes in k_find's place
@@ -3352,10 +3386,13 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
                    shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
   ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;
   ctx->last_shape[1] = tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
+  const bool flat = tab && flat_exchange_ok(g, (int)N, ctx->prof, split);
+  ctx->last_flat[0] = flat ? 1 : 0;
+  ctx->last_flat[1] = flat ? g.W * (g.threads / 64) : 0;
   if (simple)
     rc = launch_simple(ctx->stream, g, 1, jd, ctx->prof, n, (int)N, chunk, gran, gb,
                        errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr, ctx->dc.n_scalar, ctx->last_xcd[0] != 0,
-                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0);
+                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0, flat);
   else if (spread)
   {
     const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar);
@@ -4461,6 +4498,13 @@ int kss_last_shape_table(kss_ctx* ctx, int32_t* out2) {
   return 0;
 }
 
+int kss_last_simple_exchange(kss_ctx* ctx, int32_t* out2) {
+  if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
+  out2[0] = ctx->last_flat[0];
+  out2[1] = ctx->last_flat[1];
+  return 0;
+}
+
 int kss_plan_shapes(const kss_podset* ps, int32_t n_scalar, int32_t* ids, int32_t* n) {
   if (!ps || !n || ps->n_pods < 0 || (ps->n_pods > 0 && (!ids || !ps->pods)) || n_scalar < 0 || n_scalar > KSS_MAX_SCALAR)
     return fail(KSS_E_INVAL, "bad arguments");
@@ -5254,3 +5298,24 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
 }
 
 const char* kss_plan_reason(int32_t code) { return code >= 0 && code < GP_NCODES ? kGpReason[code] : "unknown"; }
+
+// k_simple_tab with the flat exchange (simple_sync_flat): every wave publishes its own entry,
+// one sweep over the W x nwave entries.  One job, not a split grid, at most SXF_MAX_E entries
+// (flat_exchange_ok).  The launch's granules: 2 x E x SXF_VALS, the XCD claim counters behind them.
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab_flat(const DevJob* __restrict__ jobs, kss_profile prof,
+                                                                     int W, int cap, int k0, int k1,
+                                                                     unsigned long long* gran, int* err,
+                                                                     unsigned long long* stamps, XPeers X, unsigned epoch0,
+                                                                     int stat_row0, int n_shapes) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const size_t gw = 2 * (size_t)W * (blockDim.x >> 6) * SXF_VALS;
+  int xs = 0;  // as k_simple
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return gw; }, W, err)) < 0) return;
+  const int w = X.xcd_local ? xs : (int)blockIdx.x;
+  if (w >= W) return;
+  const DevJob job = jobs[0];
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  simple_schedule_tab<true>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w, cap,
+                            gran, X, epoch0, err, stamps, smem, n_shapes);
+}

@@ -2090,6 +2090,205 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
   handoff_release();
 }
 
+// ---------------------------------------------------------------------------
+// The flat exchange of the table loop (k_simple_tab_flat): every WAVE publishes its own entry,
+// and wave 0 of every shard sweeps the entries of all W x nwave waves.  simple_sync_pw reduces
+// the waves of a shard first ("the best wave contributes H1, every other wave H0") and
+// simple_exchange then the shards ("the winner's shard contributes H1, every other H0"): together
+// "the winner's wave contributes H1, every other wave H0", which one sweep over the waves
+// computes by itself -- without the LDS round trip, the barrier wait and wave 0's combine
+// between a wave's statistics and its publish.
+// An entry is SXF_VALS granules {epoch << 32 | 32-bit payload}:
+//   0  the wave's best key, compressed (key_compress: the host admits the form only with key_bits > 0)
+//   1  nf0 | tt0 << 8 | nf1 << 16 | tt1 << 24   (counts <= PW_LANES per wave, raw TaintToleration <= 64)
+//   2  na0        3  na1
+// at granule (parity * E + e) * SXF_VALS + field, e = shard * nwave + wave, E = W * nwave.
+// ---------------------------------------------------------------------------
+constexpr int SXF_VALS = 4;       // granules per wave entry
+constexpr int SXF_LOADS = 8;      // sweep loads per lane: SXF_VALS * E <= 64 * SXF_LOADS
+constexpr int SXF_MAX_E = 64 * SXF_LOADS / SXF_VALS;  // 128 entries (host-checked: flat_exchange_ok)
+static_assert(PW_LANES < 256, "granule 1 packs a wave's feasible counts in 8 bits");
+
+// The entry of the wave that owns node gl (index relative to node_base) on W shards of `per`
+// nodes (the last ones shorter or empty) with nwave waves each: wave v of a shard of `own` nodes
+// owns its slots [v * pwv, v * pwv + pwv), pwv = ceil(own / nwave) (simple_schedule_tab's split).
+__host__ __device__ constexpr int flat_entry(int gl, int per, int N, int nwave) {
+  const int sh = gl / per, lo = sh * per;
+  const int own = (N - lo < per ? N - lo : per);
+  const int pwv = (own + nwave - 1) / nwave;
+  return sh * nwave + (gl - lo) / pwv;
+}
+// The nodes of entry e as first node << 8 | count (count <= PW_LANES; 0 for an empty wave or a
+// shard past W): what the sweep's lanes hold for their entries, computed once per launch, so
+// that no division stands between the winner's key and the statistics on the per-pod chain.
+__host__ __device__ constexpr uint32_t flat_entry_range(int e, int per, int N, int W, int nwave) {
+  const int sh = e / nwave, v = e - sh * nwave;
+  if (sh >= W) return 0u;
+  const int lo = sh * per;
+  const int own = N - lo < 0 ? 0 : (N - lo < per ? N - lo : per);
+  const int pwv = (own + nwave - 1) / nwave;
+  const int a = v * pwv < own ? v * pwv : own, b = a + pwv < own ? a + pwv : own;
+  return ((uint32_t)(lo + a) << 8) | (uint32_t)(b - a);
+}
+__host__ __device__ constexpr bool flat_range_holds(uint32_t r, int gl) {
+  return (uint32_t)(gl - (int)(r >> 8)) < (r & 0xFFu);  // (gl = -1, no winner: in no range)
+}
+// every node lies in the range of its entry and in no other one
+__host__ __device__ constexpr bool flat_ranges_agree(int N, int W, int nwave) {
+  const int per = (N + W - 1) / W;
+  for (int gl = 0; gl < N; gl++)
+    for (int e = 0; e < W * nwave; e++)
+      if (flat_range_holds(flat_entry_range(e, per, N, W, nwave), gl) != (e == flat_entry(gl, per, N, nwave))) return false;
+  for (int e = 0; e < W * nwave; e++)
+    if (flat_range_holds(flat_entry_range(e, per, N, W, nwave), -1)) return false;
+  return true;
+}
+static_assert(flat_ranges_agree(377, 3, 2) && flat_ranges_agree(378, 3, 2) && flat_ranges_agree(3, 3, 3) &&
+                  flat_ranges_agree(10, 2, 3) && flat_ranges_agree(9, 2, 3) && flat_ranges_agree(5, 4, 2) &&
+                  flat_ranges_agree(128, 64, 2) && flat_ranges_agree(1007, 2, 8),
+              "flat_entry_range: the lanes' ranges are flat_entry's mapping");
+// a last shard one node short: 377 nodes on 3 shards x 2 waves, shard 2 holds 125 (63 + 62)
+static_assert(flat_entry(376, 126, 377, 2) == 5 && flat_entry(314, 126, 377, 2) == 4 && flat_entry(315, 126, 377, 2) == 5 &&
+                  flat_entry(251, 126, 377, 2) == 3 && flat_entry(252, 126, 377, 2) == 4,
+              "flat_entry: last shard one node short");
+// shards of one node: the node is wave 0's, waves 1.. are empty
+static_assert(flat_entry(0, 1, 3, 3) == 0 && flat_entry(1, 1, 3, 3) == 3 && flat_entry(2, 1, 3, 3) == 6,
+              "flat_entry: shards of one node");
+// own not divisible by nwave: 10 nodes on 2 shards x 3 waves, 5 per shard as 2 + 2 + 1
+static_assert(flat_entry(1, 5, 10, 3) == 0 && flat_entry(2, 5, 10, 3) == 1 && flat_entry(4, 5, 10, 3) == 2 &&
+                  flat_entry(5, 5, 10, 3) == 3 && flat_entry(9, 5, 10, 3) == 5,
+              "flat_entry: own not divisible by nwave");
+// ... and a short last shard whose own is not divisible either: 9 nodes, shard 1 holds 4 as 2 + 2 + 0
+static_assert(flat_entry(8, 5, 9, 3) == 4 && flat_entry(6, 5, 9, 3) == 3, "flat_entry: short last shard, empty last wave");
+
+// simple_sync_pw's place in the table loop with the flat exchange.  Every wave: its statistics
+// (wave_red_stats_pw), its entry published by lanes 0..3, then its candidate to H.red for the
+// refresh (idle) and the statistics barrier -- which now overlaps the stores' way to the L2
+// instead of preceding the publish.  Wave 0 sweeps; the closing barrier hands H.res to the others.
+// No commit here (simple_schedule_tab's owner wave commits after the closing barrier).
+// R = {winner key, nf, max TT, max NA of the next pod}.  False if the launch aborted.
+template <typename Idle>
+__device__ __forceinline__ bool simple_sync_flat(SimpleHdr& H, int& parity, long long wbest, uint32_t (&u)[6], int W,
+                                                 int w, unsigned epoch, unsigned long long* gran, const XPeers& X,
+                                                 int* err, int node_base, int kb, const uint32_t (&er)[SXF_LOADS],
+                                                 long long (&R)[4], KSS_GLOBAL unsigned long long* sp, Idle&& idle) {
+  wave_red_stats_pw(u);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int E = W * nw;
+  const unsigned long long tag = (unsigned long long)epoch << 32;
+  if (sp && threadIdx.x == 0) sp[7] = wall_clock64();
+  if (lane < SXF_VALS) {
+    uint32_t x = key_compress(wbest, kb, node_base);
+    x = lane == 1 ? (u[0] | (u[1] << 8) | (u[3] << 16) | (u[4] << 24)) : x;
+    x = lane == 2 ? u[2] : x;
+    x = lane == 3 ? u[5] : x;
+    xpub(X, gran, ((size_t)(epoch & 1) * E + (size_t)w * nw + wave) * SXF_VALS + lane, tag | x);
+  }
+  // stamps: 4 wave 0 published (the two-level form's slot 4 is its one publish too), 10 / 11 waves 1 / 2 did
+  if (sp && threadIdx.x == 0) sp[4] = wall_clock64();
+  if (sp && (threadIdx.x == 64 || threadIdx.x == 128)) sp[9 + (threadIdx.x >> 6)] = wall_clock64();
+  if (lane == 0) H.red[parity][wave][0] = wbest;
+  lds_barrier();
+  if (sp && threadIdx.x == 0) sp[8] = wall_clock64();
+  idle();
+  if (wave == 0) {
+    if (sp && lane == 0) sp[15] = wall_clock64();  // sweep start (slot 15 > 0 marks the flat form)
+    const int G = SXF_VALS * E, nld = (G + 63) >> 6;
+    const unsigned long long* base = gran + (size_t)(epoch & 1) * G;
+    uint32_t got[SXF_LOADS];
+    bool done = false;
+    long long t0_ = 0;
+    for (unsigned spins = 0;; ++spins) {
+      bool ok = true;
+      unsigned long long g[SXF_LOADS];
+      // every load issued before the first is looked at (lanes past the end read granule 0)
+#pragma unroll
+      for (int i = 0; i < SXF_LOADS; i++) {
+        g[i] = tag;
+        if (i < nld) {
+          const int idx = i * 64 + lane;
+          g[i] = __hip_atomic_load(base + (idx < G ? idx : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < SXF_LOADS; i++) {
+        ok &= (g[i] >> 32) == epoch;
+        got[i] = i * 64 + lane < G ? (uint32_t)g[i] : 0u;
+      }
+      if (__all(ok)) {
+        done = true;
+        break;
+      }
+      if (spin_expired(spins, t0_)) break;
+      spin_pause();
+    }
+    if (!done) {
+      if (lane == 0) {
+        H.abort = 1;
+        err_raise(err, 1);
+      }
+    } else {
+      // lane l holds field l & 3 of the entries i * 16 + (l >> 2): the key lanes' maximum, then the wave's
+      const int field = lane & 3;
+      uint32_t k = 0;
+#pragma unroll
+      for (int i = 0; i < SXF_LOADS; i++) k = max(k, got[i]);
+      k = field == 0 ? k : 0u;
+#define KSS_KSTEP(CTRL, ROWS) k = max(k, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)k, CTRL, ROWS, 0xF, false))
+      KSS_KSTEP(0xB1, 0xF);
+      KSS_KSTEP(0x4E, 0xF);
+      KSS_KSTEP(0x141, 0xF);
+      KSS_KSTEP(0x140, 0xF);
+      KSS_KSTEP(0x142, 0xA);
+      KSS_KSTEP(0x143, 0xC);
+#undef KSS_KSTEP
+      k = (uint32_t)__builtin_amdgcn_readlane((int)k, 63);
+      const long long best = key_expand(k, kb, node_base);
+      // the winner's wave contributes its H1, every other wave its H0: er[i], the nodes of this
+      // lane's entry i * 16 + (lane >> 2) (flat_entry_range), holds the winner's node or not
+      const int gl = k ? (int)(((1u << kb) - 1u) - (k & ((1u << kb) - 1u))) : -1;
+      uint32_t nf = 0, tt = 0, na = 0;
+#pragma unroll
+      for (int i = 0; i < SXF_LOADS; i++) {
+        const bool h1 = flat_range_holds(er[i], gl);
+        const uint32_t v = got[i];
+        const uint32_t b = h1 ? v >> 16 : v;  // field 1: {nf, tt} of the hypothesis
+        nf += field == 1 ? (b & 0xFFu) : 0u;
+        tt = max(tt, field == 1 ? ((b >> 8) & 0xFFu) : 0u);
+        na = max(na, (field == 2 && !h1) || (field == 3 && h1) ? v : 0u);
+      }
+#define KSS_FSTEP(CTRL, ROWS)                                                                      \
+  {                                                                                                \
+    const uint32_t a_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nf, CTRL, ROWS, 0xF, false); \
+    const uint32_t b_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tt, CTRL, ROWS, 0xF, false); \
+    const uint32_t c_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)na, CTRL, ROWS, 0xF, false); \
+    nf += a_;                                                                                      \
+    tt = max(tt, b_);                                                                              \
+    na = max(na, c_);                                                                              \
+  }
+      KSS_FSTEP(0xB1, 0xF)
+      KSS_FSTEP(0x4E, 0xF)
+      KSS_FSTEP(0x141, 0xF)
+      KSS_FSTEP(0x140, 0xF)
+      KSS_FSTEP(0x142, 0xA)
+      KSS_FSTEP(0x143, 0xC)
+#undef KSS_FSTEP
+      if (lane == 63) {
+        H.res[0] = best;
+        H.res[1] = nf;
+        H.res[2] = tt;
+        H.res[3] = na;
+      }
+    }
+  }
+  parity ^= 1;
+  lds_barrier();
+  if (H.abort) return false;
+#pragma unroll
+  for (int i = 0; i < 4; i++) R[i] = H.res[i];
+  return true;
+}
+
 // simple_schedule<true, true, false> with the shape table (k_simple_tab): the default profile,
 // per-wave mode with at least two waves, no window, no extended resources, and a batch of at most
 // KSS_MAX_SHAPES resource shapes (SPod::shape).  The state-dependent part of an evaluation --
@@ -2112,10 +2311,14 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
 // of a pod, and written (the commit) between the closing barrier and the next statistics
 // barrier; pnd is written in the first interval and read in the second.  (So the commit is not
 // wave 0's, before the closing barrier, as in simple_sync_pw's own: commit = false there.)
+// FLAT (k_simple_tab_flat): the per-pod reduction and exchange is simple_sync_flat instead of
+// simple_sync_pw; the waves' candidates in H.red, the two barriers and everything between them
+// are the same, so the ordering above holds for both.
 // The shard load / write-back, pending outcome and prefetch below restate simple_schedule's.
 // Sharing them as inline helpers changed the code of all five loop kernels (more SGPR spill
 // traffic) and cost C1 8.6 %, pct 0 0.9 %, C2 0.3 %: profiles/r10b_loop_pieces_ab.txt.  A change
 // to one of these pieces is made in both loops.
+template <bool FLAT>
 __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __restrict__ spods,
                                                     const uint32_t* __restrict__ stat, int k0, int k1, int n_pods,
                                                     int32_t* chosen, PodMeta* meta, int W, int w, int cap,
@@ -2221,6 +2424,12 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
   const int v0 = job0 >= 0 ? job0 / n_shapes : 0, j0 = job0 >= 0 ? job0 % n_shapes : 0;
   // the shapes of pods k, k+1 (and k+2, read one pod ahead of its use)
   int ck = 0, cn = min(max(L.ring[k0 % RING].shape, 0), n_shapes - 1), cnn = 0;
+  // the flat exchange: the nodes of the entries this lane holds in the sweep (simple_sync_flat)
+  uint32_t er[SXF_LOADS] = {};
+  if constexpr (FLAT) {
+#pragma unroll
+    for (int i = 0; i < SXF_LOADS; i++) er[i] = flat_entry_range(i * 16 + (lane >> 2), per, c.N, W, nwave);
+  }
   for (int k = k0 - 1; k < k1; k++) {
     KSS_GLOBAL unsigned long long* sp = (stamps && k >= k0 && k - k0 < KSS_NSTAMP_PODS / 2)
                                             ? gstamps + (size_t)w * 8 * KSS_NSTAMP_PODS + (size_t)(k - k0) * 16
@@ -2312,9 +2521,13 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
       }
       if (tid == out_tid) store_pending();  // the previous pod's outcome
     };
-    if (!simple_sync_pw(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, false, L, kb, R, sp,
-                        idle))
-      return;
+    bool synced;
+    if constexpr (FLAT)
+      synced = simple_sync_flat(H, parity, best, u, W, w, ++epoch, gran, X, err, c.node_base, kb, er, R, sp, idle);
+    else
+      synced = simple_sync_pw(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, false, L, kb,
+                              R, sp, idle);
+    if (!synced) return;
     if (sp && tid == 0) sp[5] = wall_clock64();
     if (k >= k0) {
       const long long K = R[0];

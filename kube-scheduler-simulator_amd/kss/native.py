@@ -81,6 +81,7 @@ SIGNATURES = [
     ("kss_last_kernel", C.c_int, [C.c_void_p]),
     ("kss_last_xcd_local", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_shape_table", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("kss_last_simple_exchange", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_plan_shapes", C.c_int, [C.POINTER(abi.PodSet), C.c_int32, P(C.c_int32), P(C.c_int32)]),
     ("kss_device_go_log", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     ("kss_plan_podset", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.c_void_p]),
@@ -679,6 +680,13 @@ class Context:
         out = (C.c_int32 * 2)()
         check(lib().kss_last_shape_table(self.h, out))
         return {"shapes": out[0], "rounds": out[1]}
+
+    def last_simple_exchange(self) -> Dict[str, int]:
+        """{flat, entries} of the shape-table loop's exchange in the last run
+        (kss_last_simple_exchange); flat 0: the two-level form, or no table."""
+        out = (C.c_int32 * 2)()
+        check(lib().kss_last_simple_exchange(self.h, out))
+        return {"flat": out[0], "entries": out[1]}
 
     def last_kernel(self) -> str:
         k = lib().kss_last_kernel(self.h)

@@ -6,7 +6,11 @@ exchange done, 4 normalize pass done, 5 argmax exchange done, 6 commit + barrier
 spread / inter-pod statistics and their exchange done (inside the filter phase).
 k_simple (every shard, 16 per pod): 0 start, 1 pass B, 2 best-key reduction, 3 pass A,
 4 statistics reduction (= publish), 5 exchange + barrier, 6 commit + ring store; with the
-shape table (k_simple_tab) also 12 / 13: waves 1 / 2 finished the refresh.  For
+shape table (k_simple_tab) also 12 / 13: waves 1 / 2 finished the refresh.  The table loop's
+flat exchange (k_simple_tab_flat, every wave publishes) keeps 0-6 -- 4 is wave 0's publish, so
+3 -> 4 holds the wave reduction and the publish, 4 -> 5 the statistics barrier, the sweep and the
+closing barrier -- and adds 7 wave reduction done, 8 statistics barrier passed, 10 / 11 waves
+1 / 2 published, 15 sweep start (slot 15 > 0 marks the form).  For
 k_simple the arrival skew of the exchange is reported: per pod, the spread of the
 shards' publish times, and the wait from the LAST publish to each shard's completion
 (propagation + reductions).
@@ -75,7 +79,10 @@ def summarise(path):
                      f" latest shard most often {int(late.argmax())} ({late.max()}/{good.sum()} pods)")
             pa = (a[:, :, 3] - a[:, :, 0]) / 100.0
             line += f"\n  start -> passA done per shard: median {np.median(pa[:, good]):.2f} us, max over shards (median) {np.median(pa[:, good].max(axis=0)):.2f}"
-        if ((s0[ok, 7] > 0) & (s0[ok, 8] > 0)).any():  # per-wave mode: statistics reduction detail
+        flat = (s0[ok, 15] > 0).any()
+        if flat:
+            line += flat_detail(s0[ok])
+        elif ((s0[ok, 7] > 0) & (s0[ok, 8] > 0)).any():  # per-wave mode: statistics reduction detail
             q = s0[ok][(s0[ok, 7] > 0) & (s0[ok, 8] > 0)]
             seq = np.stack([q[:, 3], q[:, 7], q[:, 8], q[:, 4]], axis=1)
             dd = np.median(np.diff(seq, axis=1) / 100.0, axis=0)
@@ -95,6 +102,25 @@ def summarise(path):
             line += window_detail(s0[ok])
         lines.append(line)
     return "\n".join(lines)
+
+
+def flat_detail(s):
+    """The flat exchange on shard 0: passA done (3) -> wave reduction (7) -> wave 0 published (4) ->
+    statistics barrier passed (8) -> sweep start (15) -> sweep, H.res and closing barrier (5);
+    and which wave of the shard published last (4, 10, 11: waves 0, 1, 2)."""
+    q = s[(s[:, 7] > 0) & (s[:, 8] > 0) & (s[:, 15] > 0)]
+    seq = np.stack([q[:, 3], q[:, 7], q[:, 4], q[:, 8], q[:, 15], q[:, 5]], axis=1)
+    dd = np.median(np.diff(seq, axis=1) / 100.0, axis=0)
+    line = (f"\n  flat exchange (shard 0): wave_red={dd[0]:.2f} publish={dd[1]:.2f} write+barrier={dd[2]:.2f}"
+            f" idle={dd[3]:.2f} sweep+closing barrier={dd[4]:.2f} us")
+    pubs = np.stack([q[:, 4], q[:, 10], q[:, 11]], axis=1)
+    have = (pubs > 0).all(axis=1)
+    if have.any():
+        late = np.bincount(pubs[have].argmax(axis=1), minlength=3)
+        lag = (pubs[have].max(axis=1) - pubs[have, 0]) / 100.0
+        line += (f"\n  last publisher of shard 0's waves 0 / 1 / 2: {late[0]} / {late[1]} / {late[2]} of {int(have.sum())} pods;"
+                 f" last publish after wave 0's: median {np.median(lag):.2f} us")
+    return line
 
 
 def window_detail(s):
