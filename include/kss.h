@@ -718,7 +718,13 @@ int kss_axis_commit(kss_ctx* ctx, int32_t pod_index, const int64_t* key_dev, con
  * kernels' own granule exchanges: each granule is stored into every part's inbox (xGMI
  * peer stores) and polled in the local inbox, so a pod costs no launch and no host round
  * trip on any GPU.  Every part ends with the full chosen / outcome vectors; node state is
- * current on each part for its own rows.
+ * current on each part for its own rows.  What runs: staged, unrecorded batches (kss_run_staged)
+ * that k_simple or k_spread take, at any pct_nodes_to_score.  Below 100 the kernels run
+ * findNodesThatPassFilters' window across the parts, and every launch leaves the same
+ * nextStartNodeIndex in every part's cursor word (kss_next_start_node_index; set the same value on
+ * every part with kss_set_next_start_node_index).  Refused (KSS_E_UNSUPPORTED): batches that need
+ * k_schedule -- under a window those with PreFilterResult name lists, or k_spread programs with a
+ * custom profile -- recorded batches, and nominated pods.
  *   kss_split_config  allocates the zeroed inbox (n_parts == 1 clears the split) and moves the
  *                     context to a stream with a hardware queue of its own (parts that share one
  *                     of the runtime's GPU_MAX_HW_QUEUES queues would run one after the other)

@@ -2784,6 +2784,10 @@ static void split_chunk_view(const SplitRun& sr, int ci, unsigned long long* gra
   g_out = gran + off;
 }
 
+// Granule epochs of one chunk launch.  The most a pod takes is k_spread's five (statistics, the
+// window's count exchange, filter, normalisation, argmax); k_simple takes one per pod, one for the
+// prologue and, for a window on a split grid, one for the end-of-launch cursor granule: all
+// within 8 per pod + 16.
 static unsigned chunk_span(int pods) { return 8u * (unsigned)std::max(pods, 1) + 16u; }
 
 static void static_rows(const Geometry& g, const XPeers& X, int max_nodes, int& n_lo, int& n_hi) {
@@ -2827,7 +2831,8 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   // k_simple of chunk i-1 (the last reader of that half)
   int cap = simple_cap(g);
   const bool def = same_profile(prof, default_profile_c());
-  // k_find > 0: the percentageOfNodesToScore window (one job, not split)
+  // k_find > 0: the percentageOfNodesToScore window (one job; on a split grid every part ends the
+  // launch with the same nextStartNodeIndex in its own cursor word, simple_schedule)
   const bool win = k_find > 0;
   // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
   const bool tab = n_shapes > 0 && def && !win && nsc == 0;
@@ -3148,11 +3153,13 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   // percentageOfNodesToScore below 100: findNodesThatPassFilters' window (numFeasibleNodesToFind,
   // nextStartNodeIndex) runs on k_schedule only; its per-shard count exchange needs W + 1 values
   const bool window = ctx->prof.pct_nodes_to_score < 100;
-  // k_simple runs the window itself (simple_sync_win) for pods without a PreFilterResult list on an
-  // unsplit grid; k_find = N: the list is too short for a window (every node processed)
+  // k_simple runs the window itself (simple_sync_win) for pods without a PreFilterResult list, on
+  // one part or on a split grid; k_find = N: the list is too short for a window (every node processed)
   const int k_find = window ? num_feasible_to_find((int)N, ctx->prof.pct_nodes_to_score) : (int)N;
-  const bool simple_win_ok = !window || k_find >= (int)N || (!split && !ctx->staged_names);
-  if (window) W = std::min(W, XW_MAX - NSCAL);  // k_schedule's window exchange: W + 1 values
+  const bool simple_win_ok = !window || k_find >= (int)N || !ctx->staged_names;
+  // k_schedule's window exchange: W + 1 values.  Not a split grid's limit: its W is fixed by the
+  // parts and it runs a loop kernel or nothing (the loop kernels' own limits are checked below)
+  if (window && !split) W = std::min(W, XW_MAX - NSCAL);
   // nominated pods (kss_nominate): RunFilterPluginsWithNominatedPods and PreferNominatedNode run on
   // k_schedule only
   const bool nomq = !ctx->nom.empty();
@@ -3173,9 +3180,9 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   const double count_total = ctx->count_bound + (commit ? (double)n * (1.0 + ctx->staged_max_own) : 0.0);
   const double cell_total = ctx->cell_bound + (commit ? (double)n * ctx->gneed.max_mult : 0.0);
   // k_spread runs the window itself (spread_schedule WIN) for default-profile pods without a
-  // PreFilterResult list on an unsplit grid, the statistics fold off
+  // PreFilterResult list, the statistics fold off (one part or a split grid)
   const bool spread_win = window && k_find < (int)N;
-  const bool spread_win_ok = !spread_win || (!split && !ctx->staged_names && !opt(O_FOLD) &&
+  const bool spread_win_ok = !spread_win || (!ctx->staged_names && !opt(O_FOLD) &&
                                              same_profile(ctx->prof, default_profile_c()));
   const bool spread_ok = spread_win_ok && !nomq && staged && ctx->gpod_ok && commit && !record && !keep_norm && need.general &&
                          scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
@@ -3256,6 +3263,26 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (split && !loop)
     return fail(KSS_E_UNSUPPORTED, spread_ok ? "split grid: a k_spread shard exceeds LDS (more shards per part)"
                                              : "split grid: the batch needs k_schedule (kss_plan_podset)");
+  // The window on a split grid, before any epoch is assigned: the limits of the loop kernels' own
+  // window exchanges (k_simple's sweep of 64 * SX_CHUNKS shards is refused above).
+  const int win_find = k_find < (int)N ? k_find : 0;
+  if (split && win_find > 0) {
+    const size_t half = ctx->split_inbox_bytes / 2 / sizeof(unsigned long long);
+    if (simple) {
+      // statistics granules of both epoch parities, the cut granules, the end-of-launch cursor granule
+      if (sxw_words(g.W) > half) return fail(KSS_E_UNSUPPORTED, "split grid: k_simple's window granules exceed an inbox half");
+    } else {
+      // the count exchange: W SUM values behind the pod's bins and one scalar, per shard and parity
+      GpodNeeds qw = ctx->gneed;
+      qw.bins_cap += g.W;
+      qw.xw = std::max(qw.xw, g.W + 1);
+      if (g.W + 1 > G_XW) return fail(KSS_E_UNSUPPORTED, "split grid: k_spread's window count vector exceeds G_XW values (fewer shards)");
+      if (2 * (size_t)g.W * (size_t)qw.gs() > half)
+        return fail(KSS_E_UNSUPPORTED, "split grid: k_spread's window count vector exceeds an inbox half");
+      if (!spread_fits(g, qw, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar))
+        return fail(KSS_E_UNSUPPORTED, "split grid: k_spread's window count bins exceed LDS (more shards per part)");
+    }
+  }
   const int chunk = loop ? static_chunk(N, n) : 0;
   if (loop && (rc = ctx->stat_buf.ensure(sizeof(uint32_t) * (size_t)chunk * std::max<size_t>(N, 1)))) return rc;
   DevJob job{};
@@ -3381,7 +3408,6 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   ctx->last_xcd[0] = (simple && xcd_try && g.W > 1) || xcd_spread ? 1 : 0;
   ctx->last_xcd[1] = 0;
   // the shape table: the whole staged batch (its shape directory sits in its first records)
-  const int win_find = k_find < (int)N ? k_find : 0;
   const bool tab = simple && opt(O_SHAPE_TABLE) && n == ctx->staged_n &&
                    shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
   ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;

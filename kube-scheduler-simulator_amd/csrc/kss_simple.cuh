@@ -1271,6 +1271,9 @@ __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long l
 // Statistics index: (h * 2 + part) * 3 + {0 F, 1 TT, 2 NA}, h = 0 H0, 1 H1.
 constexpr int SXW_VALS = 10;  // granules per shard: key lo / hi, then {F << 16 | TT, NA} of a0, b0, a1, b1
 constexpr int SXW_E2 = 4;     // the cut shard's granules per epoch parity: d, TT, NA (+ pad)
+constexpr int SXW_CUR = 2;    // split grids: the end-of-launch cursor granule behind the cut granules (+ pad)
+// The window's granules of one launch (8-byte words of the exchange buffer / an inbox half).
+constexpr size_t sxw_words(int W) { return 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 + SXW_CUR; }
 
 __device__ __forceinline__ void win_acc(uint32_t (&u)[12], bool c0, bool c1, int part, const SVal& e) {
 #pragma unroll
@@ -1803,7 +1806,8 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
 // word is set and the shard leaves without writing node state back.  PW: per-wave mode
 // (simple_sync_pw; the caller checks that every shard's nodes fit it).  WIN: percentageOfNodesToScore
 // < 100 (simple_sync_win): k_find = numFeasibleNodesToFind, cursor = the cluster's nextStartNodeIndex
-// word (read at the start, written back by shard 0 at the end).
+// word (read at the start; written back at the end by the start shard, on a split grid by the first
+// shard of every part from the start shard's granule).
 template <bool DEF, bool PW, bool WIN>
 __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __restrict__ spods,
                                                 const uint32_t* __restrict__ stat, const int32_t* __restrict__ ints,
@@ -2075,9 +2079,42 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
   if (tid == out_tid) store_pending();  // the last pod's outcome
   // nextStartNodeIndex after the last pod: the start shard of the pod after it writes it (the last
   // iteration's pass A, for no pod, already moved the start past the last pod's cut)
-  if (WIN && cursor && w == wss && tid == 0) st_ag(cursor, (int32_t)wsx);
+  if constexpr (WIN) {
+    if (X.n <= 1) {
+      if (cursor && w == wss && tid == 0) st_ag(cursor, (int32_t)wsx);
+    } else {
+      // Split grid: every part has a cursor word of its own, read by its next chunk launch and its
+      // next run, and only the start shard knows s.  It publishes s as one more epoch-tagged
+      // granule into every part's inbox (SXW_CUR, behind the cut granules); the first shard of
+      // each part polls its local copy and stores the part's word.  One granule per launch and
+      // inbox half: a part one chunk ahead publishes its next cursor into the OTHER half (the
+      // halves alternate by chunk), and this address is written again only two chunks later, at
+      // the end of a launch whose per-pod exchanges need every part -- so behind this part's poll,
+      // which precedes that launch in its stream.  The tag is above every tag the loop used.
+      const size_t co = 2 * (size_t)W * SXW_VALS + 2 * SXW_E2;
+      ++epoch;
+      if (w == wss && tid == 0) xpub(X, gran, co, ((unsigned long long)epoch << 32) | (uint32_t)wsx);
+      if (w == X.w_off && tid == 0) {
+        long long t0_ = 0;
+        for (unsigned spins = 0;; ++spins) {
+          const unsigned long long g = __hip_atomic_load(gran + co, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if ((g >> 32) == epoch) {
+            if (cursor) st_ag(cursor, (int32_t)(uint32_t)g);
+            break;
+          }
+          if (spin_expired(spins, t0_)) {
+            H.abort = 1;
+            err_raise(err, 1);
+            break;
+          }
+          spin_pause();
+        }
+      }
+    }
+  }
   // node state back to HBM
   __syncthreads();
+  if (WIN && X.n > 1 && H.abort) return;  // as every exchange timeout: no node state written back
   for (int s = tid; s < own; s += nt) {
     const int n = lo + s;
 #pragma unroll

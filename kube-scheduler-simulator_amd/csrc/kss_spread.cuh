@@ -1513,7 +1513,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
                                                 unsigned long long* stamps, int nst, const HandoffCheck& hc,
                                                 long long* smem, int k_find = 0, int32_t* cursor = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
-  // WIN: nextStartNodeIndex for the launch (every shard holds the same value; shard 0 writes it back)
+  // WIN: nextStartNodeIndex for the launch (every shard holds the same value and writes it back, each part into its own word)
   int wstart = WIN && cursor && c.N > 0 ? (int)(((long long)ld_ag(cursor) % c.N + c.N) % c.N) : 0;
   SpreadHdr& H = *reinterpret_cast<SpreadHdr*>(smem);
   const SpreadShard L = spread_view(smem, cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD);
@@ -2339,7 +2339,12 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
 #undef GSTAMP
   }
   // node state and the resident count rows back to HBM
-  if (WIN && cursor && w == 0 && tid == 0) *cursor = wstart;  // stream order: the next launch reads it
+  // nextStartNodeIndex: every shard holds the same value (the stopping node rides the filter exchange),
+  // and every shard stores it into its own context's word -- on a split grid each part's next chunk
+  // launch and next run read their own.  Identical agent-scope stores, ahead of the hand-off release
+  // below; no shard test: a value of X kept live to the end of the loop costs the window kernels
+  // SGPR spills and AGPRs (C3 at pct 0: -1.9 %).  The next launch reads the word in stream order.
+  if (WIN && cursor && tid == 0) st_ag(cursor, (int32_t)wstart);
   __syncthreads();
   if (stl)
     for (int i = tid; i < 16 * nst; i += nt) stamps[(size_t)w * 8 * KSS_NSTAMP_PODS + i] = stl[i];

@@ -5,7 +5,9 @@ Every part loads the whole cluster and stages the same pods; part p runs shards
 node rows.  The per-pod exchanges the kernels already make between their shards
 (statistics, PodTopologySpread histograms and critical paths, the packed selectHost key)
 become cross-GPU by storing every granule into every part's inbox: xGMI peer stores from
-inside the running kernels, polled locally.  A pod costs no kernel launch, no collective
+inside the running kernels, polled locally.  A profile with pct_nodes_to_score < 100 (the
+simulator's own setting) runs findNodesThatPassFilters' window across the parts; each launch
+leaves the same nextStartNodeIndex in every part's cursor word.  A pod costs no kernel launch, no collective
 call and no host round trip on any GPU -- the replacement for the per-pod RCCL packed-argmax
 all-reduce of kss/nodeaxis.py, which pays two launches and two collectives per pod.
 
@@ -118,6 +120,20 @@ class InProcessSplit:
         for c in self.ctxs:
             c.reset()
 
+    def set_next_start_node_index(self, v: int):
+        """nextStartNodeIndex of the whole grid: every part's cursor word (a windowed run,
+        pct_nodes_to_score < 100, starts its first pod's search there)."""
+        for c in self.ctxs:
+            c.set_next_start_node_index(v)
+
+    def next_start_node_index(self) -> int:
+        """The grid's nextStartNodeIndex.  Every launch leaves the same value in every part's word;
+        parts that disagree are a bug, reported and never averaged away."""
+        vs = [c.next_start_node_index() for c in self.ctxs]
+        if any(v != vs[0] for v in vs):
+            raise RuntimeError(f"split grid: the parts' nextStartNodeIndex differ: {vs}")
+        return vs[0]
+
     def node_state(self):
         """The cluster's mutable columns assembled from the parts' own rows."""
         out = None
@@ -169,6 +185,16 @@ class SplitRank:
 
     def run(self, n: int) -> np.ndarray:
         return self.ctx.run_staged(n)
+
+    def set_next_start_node_index(self, v: int):
+        """This rank's cursor word.  Every rank must set the same value before a windowed run: the
+        parts split each pod's node list at it, and nothing exchanges it at the start of a run."""
+        self.ctx.set_next_start_node_index(v)
+
+    def next_start_node_index(self) -> int:
+        """nextStartNodeIndex as this rank's part left it (every launch ends with the same value on
+        every rank)."""
+        return self.ctx.next_start_node_index()
 
     def rows(self) -> Tuple[int, int]:
         return part_rows(self.n_nodes, self.world, self.wl, self.rank)
