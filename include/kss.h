@@ -551,7 +551,14 @@ int kss_eval_pod_view(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, uin
  *                       grid too) and stop.  The grid leaves by itself after ~1 s without a
  *                       command and is restarted by the next call.  Every other entry point
  *                       that touches the context's device state stops it first.
- * Results equal kss_eval_pod_view / kss_commit / kss_rollback on the same state.
+ * Results equal kss_eval_pod_view / kss_commit / kss_rollback on the same state, the nominator
+ * (kss_nominate) included: the grid reads the table as it stood at its (re)start -- the calls
+ * that change it stop the grid first, like every entry point that touches device state, and the
+ * next service call restarts it -- and filters with RunFilterPluginsWithNominatedPods /
+ * PreferNominatedNode as kss_eval_pod does.  The identities are the staged pods' (kss_pod.uid
+ * when > 0, else the staged index; index-keyed entries of another pod list, or whose staged pod
+ * differs, are dropped at the start).  kss_service_commit removes the assumed pod's nomination
+ * (DeleteNominatedPodIfExists, as kss_commit); kss_service_rollback does not restore it.
  * The resident grid runs on a stream with a hardware queue of its own (a CU-masked stream: the
  * runtime's GPU_MAX_HW_QUEUES shared queues are not used), so no other context's or stream's
  * work waits behind it; the grid's workgroups still occupy CUs until it leaves. */
@@ -592,7 +599,8 @@ int kss_service_stamps(kss_ctx* ctx, uint64_t* out8);
  * volumes or extended resources; below percentageOfNodesToScore 100 no PreFilterResult node
  * lists, the window running on the same chain) with the record stored from
  * registers, 2 the same on an XCD-local grid (its exchanges in one XCD's L2), 0 the general
- * chain (schedule_pod + the record copy), -1 not started. */
+ * chain (schedule_pod + the record copy), -1 not started.  A non-empty nominator does not change
+ * the mode: each chain has an instantiation that reads the table, launched while it holds entries. */
 int kss_service_mode(kss_ctx* ctx, int32_t* mode);
 /* commit pod ps.pods[pod_index] to node (AssumePod); rollback undoes it (Unreserve/ForgetPod).
  * The deltas travel in the kernel's arguments (no upload). */
@@ -633,21 +641,24 @@ int kss_set_next_start_node_index(kss_ctx* ctx, int32_t value);
  *   kss_nominate          AddNominatedPod: ps.pods[pod_index] is nominated to global node `node`
  *                         (an earlier nomination of the same pod is replaced).  The pod's identity
  *                         is kss_pod.uid when > 0, otherwise its index in the podset the caller
- *                         schedules from (the staged one for batches, the one passed to
- *                         kss_eval_pod).  At most 64 entries; pods with volumes are refused.
+ *                         schedules from (the staged one for batches and the service grid, the
+ *                         one passed to kss_eval_pod).  At most 64 entries; pods with volumes
+ *                         are refused.
  *   kss_clear_nomination  DeleteNominatedPodIfExists (a PostFilter that found no candidate, a
  *                         lower-priority nomination cleared by prepareCandidate); no-op if absent
  *   kss_nominations       the entries in AddNominatedPod order (*n = count; cap entries copied)
- * Every scheduling cycle (kss_eval_pod, batches, kss_postfilter_pod's dry run) then filters with
+ * Every scheduling cycle (kss_eval_pod, kss_service_eval, batches, kss_postfilter_pod's dry run)
+ * then filters with
  * RunFilterPluginsWithNominatedPods: on a node holding nominees of priority >= the pod's (other
  * than the pod itself) the filters run first with them added (their requests, pod count, host
  * ports, and their labels / required anti-affinity terms in the PodTopologySpread and
  * InterPodAffinity counts of the node's pairs); a failure there is the node's status, otherwise
  * the plain pass decides.  A nominated pod first evaluates its own node (PreferNominatedNode:
  * chosen without scoring when it passes; nextStartNodeIndex restarts at 0).  An assumed pod leaves
- * the nominator (kss_commit, batch commits).  kss_load_cluster / kss_reset_node_state empty it.
- * While it is non-empty batches run on k_schedule and the service grid, node axis and split
- * grids refuse (KSS_E_UNSUPPORTED).  Replaces the nominator of the scheduler that
+ * the nominator (kss_commit, kss_service_commit, batch commits).  kss_load_cluster /
+ * kss_reset_node_state empty it.  While it is non-empty batches run on k_schedule, the service
+ * grid runs the instantiations that read it (restarted by the next service call after every
+ * change of the table), and the node axis and split grids refuse (KSS_E_UNSUPPORTED).  Replaces the nominator of the scheduler that
  * simulator/scheduler/scheduler.go:155-168 creates (pkg/scheduler/internal/queue, v1.26). */
 int kss_nominate(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, int32_t node);
 int kss_clear_nomination(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index);

@@ -304,8 +304,10 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_schedule(const DevJob* __re
 }
 
 // The per-pod service grid (kss_service.cuh): W shards of one cluster, commands from the
-// pinned ring starting at command `seq`.
-template <bool GEN, bool SIMPLE, bool INL = false>
+// pinned ring starting at command `seq`.  NOM: the grid reads the nominator's table (job.nom);
+// instantiations of their own, launched only while the table is not empty, so the kernels of the
+// empty nominator keep their code and register allocation.
+template <bool GEN, bool SIMPLE, bool INL = false, bool NOM = false>
 __global__ __launch_bounds__(KSS_MAX_THREADS) void k_service(const DevJob* __restrict__ jobs, kss_profile prof, int W,
                                                              int npt, int bins_cap, int cache_keys,
                                                              unsigned long long* gran, int* err, SvcBox* box,
@@ -314,8 +316,8 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_service(const DevJob* __res
                                                              int xcd) {
   extern __shared__ __attribute__((aligned(16))) long long smem[];
   const DevJob job = jobs[0];
-  service_loop<GEN, SIMPLE, INL>(job.c, job, prof, W, npt, bins_cap, cache_keys, gran, err, box, relay, seen, rec_host,
-                                 seq, 0u, stamps, smem, xcd);
+  service_loop<GEN, SIMPLE, INL, NOM>(job.c, job, prof, W, npt, bins_cap, cache_keys, gran, err, box, relay, seen, rec_host,
+                                      seq, 0u, stamps, smem, xcd);
 }
 
 // grid = n_jobs * W, as k_schedule; each shard's nodes live in LDS (cap slots).
@@ -768,6 +770,7 @@ struct kss_ctx {
   std::vector<DevNom> nom;
   std::unordered_map<int32_t, const kss_podset*> nom_src;  // index-keyed entries: the podset they index
   std::vector<int32_t> staged_uid;  // the staged pods' nominator identities (batch commits leave it)
+  const kss_podset* staged_ps = nullptr;  // the staged list's address (compared, never read: nom_check_staged)
   DevBuf nom_buf;
   bool nom_dirty = true;
   int32_t run_pod_base = 0;
@@ -873,6 +876,12 @@ struct kss_ctx {
     bool simple = false;  // the k_simple-shaped evaluation (svc_simple_eval)
     DevBuf stat;          // its static words of every staged pod (k_static at the start)
     bool xcd = false;     // ... on an XCD-local grid (xcd_slot)
+    // the nominator as the grid reads it: uploaded by every (re)launch (svc_launch), with the
+    // host copies the uploads read from
+    DevBuf nomtab;
+    std::vector<DevNom> nom_host;
+    DevJob job_host{};
+    size_t shmem_nom = 0;  // LDS of a launch that reads the table (SIMPLE: + 8 bytes per node slot)
   } svc;
   // split grid (kss_split_*): this context runs part split_part of split_n, split_wl shards
   // each; split_inbox is its exchange inbox (uncached device memory, zeroed once), split_peer
@@ -2153,6 +2162,22 @@ int kss_next_start_node_index(kss_ctx* ctx, int32_t* out) {
   return 0;
 }
 
+// The nominator entry of a pod from its bound-table form (bound_from_pod; the staged pods' copies
+// in ctx->staged_bp): the one place that fills a DevNom, so nom_entry and nom_check_staged agree.
+static BoundPod bound_from_pod(const kss_podset* ps, int i);
+static DevNom nom_from_bound(const BoundPod& b, int32_t pod, int32_t local) {
+  DevNom e{};
+  e.node = local;
+  e.prio = b.prio;
+  e.pod = pod;
+  e.cls = b.cls;
+  e.n_terms = b.tlen;
+  for (int t = 0; t < b.tlen; t++) e.terms[t] = b.terms[t];
+  e.ports = b.ports;
+  for (int r = 0; r < KSS_NRES; r++) e.req[r] = b.req[r];
+  return e;
+}
+
 // The nominator entry of ps.pods[pod_index] on local row `local` (AddNominatedPod's NominatedPod)
 static int nom_entry(const kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, int32_t local, DevNom& e) {
   const kss_pod& p = ps->pods[pod_index];
@@ -2163,18 +2188,9 @@ static int nom_entry(const kss_ctx* ctx, const kss_podset* ps, int32_t pod_index
   if (p.own_terms_len > 8) return fail(KSS_E_UNSUPPORTED, "a nominated pod with more than 8 own term rows");
   if (ctx->host.n_ports < KSS_MAX_PORTS && (p.port_add >> ctx->host.n_ports))
     return fail(KSS_E_INVAL, "pod port bit outside the port dictionary");
-  e = DevNom{};
-  e.node = local;
-  e.prio = p.priority;
-  e.pod = pod_identity(p, pod_index);
-  e.cls = p.cls;
-  e.n_terms = p.own_terms_len;
-  for (int t = 0; t < p.own_terms_len; t++) {
-    e.terms[t] = ps->ints[p.own_terms_off + t];
+  e = nom_from_bound(bound_from_pod(ps, pod_index), pod_identity(p, pod_index), local);  // (at most 8 rows: above)
+  for (int t = 0; t < e.n_terms; t++)
     if (e.terms[t] < 0 || e.terms[t] >= ctx->host.n_terms) return fail(KSS_E_INVAL, "own term id out of range");
-  }
-  e.ports = p.port_add;
-  for (int r = 0; r < KSS_NRES; r++) e.req[r] = p.commit_req[r];
   return 0;
 }
 
@@ -2196,6 +2212,29 @@ static void nom_check_podset(kss_ctx* ctx, const kss_podset* ps) {
                                   if (idx >= ps->n_pods || ps->pods[idx].uid > 0) return true;
                                   DevNom now;
                                   if (nom_entry(ctx, ps, idx, e.node, now)) return true;
+                                  return std::memcmp(&now, &e, sizeof(DevNom)) != 0;
+                                }),
+                 ctx->nom.end());
+  if (ctx->nom.size() != before) ctx->nom_dirty = true;
+}
+
+// The same for the service grid, whose calls name staged pods by index: an index-keyed entry must
+// belong to the staged list (its address is compared, never read: the caller may have freed the
+// list since it staged it) and equal the entry of the pod staged at that index (nom_from_bound of
+// the host copy stage_bound kept, as nom_entry builds it).  Call with ctx->mu held.
+static void nom_check_staged(kss_ctx* ctx) {
+  if (ctx->nom.empty()) return;
+  const size_t before = ctx->nom.size();
+  ctx->nom.erase(std::remove_if(ctx->nom.begin(), ctx->nom.end(),
+                                [&](const DevNom& e) {
+                                  if (e.pod >= 0) return false;
+                                  auto it = ctx->nom_src.find(e.pod);
+                                  if (it == ctx->nom_src.end() || it->second != ctx->staged_ps) return true;
+                                  const size_t idx = (size_t)(-1 - e.pod);
+                                  if (idx >= (size_t)std::max(ctx->staged_n, 0) || idx >= ctx->staged_bp.size() ||
+                                      idx >= ctx->staged_uid.size() || ctx->staged_uid[idx] != e.pod)
+                                    return true;
+                                  const DevNom now = nom_from_bound(ctx->staged_bp[idx], e.pod, e.node);
                                   return std::memcmp(&now, &e, sizeof(DevNom)) != 0;
                                 }),
                  ctx->nom.end());
@@ -3964,6 +4003,7 @@ int kss_schedule_batch(kss_ctx* ctx, const kss_podset* ps, int32_t n, uint32_t f
   if (rc) return rc;
   if ((rc = stage_spods(ctx, ps))) return rc;
   stage_bound(ctx, ps);
+  ctx->staged_ps = ps;
   ctx->staged_n = ps->n_pods;
   ctx->staged_need = plan_needs(ctx->key_card_h.data(), ctx->key_flags_h.data(), ps, ps->n_pods);
   rc = run_single(ctx, ctx->staged_need, ctx->dp, n, /*commit=*/true, record, /*keep_norm=*/record, flags, chosen_out,
@@ -3987,6 +4027,7 @@ int kss_stage_pods(kss_ctx* ctx, const kss_podset* ps) {
   if (rc) return rc;
   if ((rc = stage_spods(ctx, ps))) return rc;
   stage_bound(ctx, ps);
+  ctx->staged_ps = ps;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   ctx->staged_n = ps->n_pods;
   ctx->staged_need = plan_needs(ctx->key_card_h.data(), ctx->key_flags_h.data(), ps, ps->n_pods);
@@ -4032,6 +4073,7 @@ static void svc_free(kss_ctx* ctx) {
   svc_free_rec(v);
   if (v.stream) hipStreamDestroy(v.stream);
   v.relay.release();
+  v.nomtab.release();
   v.stat.release();
   v.gran.release();
   v.err.release();
@@ -4056,11 +4098,32 @@ static int svc_launch(kss_ctx* ctx) {
   HIP_TRY(dev_zero(v.err.p, 16, v.stream));  // the error word and xcd_slot's two counters
   v.box->err = 0;
   v.box->xcd_fail = 0;
+  // the nominator's table as it stands now (the stream is idle: no earlier copy still reads the
+  // host copies): entries the service's commits removed since the last launch are gone, and the
+  // grid starts with every uploaded entry nominated
+  const bool nomq = !ctx->nom.empty();
+  if (nomq || v.job_host.n_nom) {
+    v.nom_host = ctx->nom;
+    if (nomq) {
+      if (int rc = v.nomtab.ensure(sizeof(DevNom) * v.nom_host.size())) return rc;
+      HIP_TRY(hipMemcpyAsync(v.nomtab.p, v.nom_host.data(), sizeof(DevNom) * v.nom_host.size(), hipMemcpyHostToDevice,
+                             v.stream));
+    }
+    v.job_host.nom = nomq ? (const DevNom*)v.nomtab.p : nullptr;
+    v.job_host.n_nom = (int32_t)v.nom_host.size();
+    HIP_TRY(hipMemcpyAsync(v.job.p, &v.job_host, sizeof(DevJob), hipMemcpyHostToDevice, v.stream));
+  }
   const bool inl = opt(O_SVC_INLINE_SWEEP) != 0;
   const void* fn = v.gen ? (const void*)k_service<true, false>
                          : (v.simple ? (inl ? (const void*)k_service<false, true, true> : (const void*)k_service<false, true>)
                                      : (const void*)k_service<false, false>);
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.shmem));
+  // (the svc_inline_sweep option has no NOM instantiation: a grid that reads the nominator runs
+  // the out-of-line sweep whatever the option says)
+  if (nomq)
+    fn = v.gen ? (const void*)k_service<true, false, false, true>
+               : (v.simple ? (const void*)k_service<false, true, false, true> : (const void*)k_service<false, false, false, true>);
+  const size_t shmem = nomq ? v.shmem_nom : v.shmem;
+  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   const DevJob* jd = (const DevJob*)v.job.p;
   kss_profile pr = ctx->prof;
   int W = v.W, npt = v.npt, bins = v.bins_cap, ck = v.cache_keys;
@@ -4079,7 +4142,7 @@ static int svc_launch(kss_ctx* ctx) {
                   (void*)&err, (void*)&box, (void*)&relay, (void*)&seenp, (void*)&rec, (void*)&s0, (void*)&stamps,
                   (void*)&xcd};
   const unsigned grid = (unsigned)(v.xcd ? XCD_GRID_MULT * W : W);
-  if (int rc = launch_resident(fn, dim3(grid), dim3((unsigned)v.threads), args, v.shmem, v.stream)) return rc;
+  if (int rc = launch_resident(fn, dim3(grid), dim3((unsigned)v.threads), args, shmem, v.stream)) return rc;
   v.running = true;
   return 0;
 }
@@ -4089,8 +4152,7 @@ static int svc_start_locked(kss_ctx* ctx) {
   if (!ctx->loaded) return fail(KSS_E_INVAL, "no cluster loaded");
   if (ctx->staged_n <= 0) return fail(KSS_E_INVAL, "the service evaluates staged pods: kss_stage_pods first");
   if (ctx->split_n > 1) return fail(KSS_E_UNSUPPORTED, "the service runs the whole cluster on one device");
-  if (!ctx->nom.empty())
-    return fail(KSS_E_UNSUPPORTED, "the service grid does not read the nominator: kss_eval_pod / batches while pods are nominated");
+  nom_check_staged(ctx);
   auto& v = ctx->svc;
   HIP_TRY(hipSetDevice(ctx->cfg.device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));  // every earlier launch / copy on the ctx stream is done
@@ -4179,7 +4241,10 @@ static int svc_start_locked(kss_ctx* ctx) {
   job.slot_bytes = SL.bytes;
   job.prof = ctx->prof;
   job.cursor = (int32_t*)ctx->cursor_buf.p;
-  v.simple = simple_pre && cache_keys >= 0 && g.W <= 64;
+  // (a grid that reads the nominator keeps 8 more bytes of LDS per node slot: SvcNom::here)
+  const size_t lds_cached = base + (cache_keys >= 0 ? node_cache_bytes(cap, cache_keys) : 0);
+  const bool nom_lds_ok = ctx->nom.empty() || lds_cached + 8 * (size_t)cap <= KSS_LDS_BUDGET;
+  v.simple = simple_pre && cache_keys >= 0 && g.W <= 64 && nom_lds_ok;
   v.xcd = v.simple && xcd_ok && g.W <= xcd_cus && g.W > 1;
   job.spods = v.simple ? (const SPod*)ctx->spod_buf.p : nullptr;
   // the static words of every staged pod (4 bytes per pod and node, at most 4 GiB): one load per
@@ -4188,7 +4253,8 @@ static int svc_start_locked(kss_ctx* ctx) {
   const bool pre_static = v.simple && stat_bytes <= ((size_t)4 << 30) && !opt(O_SVC_NO_STATIC);
   if (pre_static && (rc = v.stat.ensure(stat_bytes))) return rc;
   job.stat = pre_static ? (uint32_t*)v.stat.p : nullptr;
-  HIP_TRY(hipMemcpyAsync(v.job.p, &job, sizeof(DevJob), hipMemcpyHostToDevice, v.stream));
+  v.job_host = job;  // (nom / n_nom: svc_launch)
+  HIP_TRY(hipMemcpyAsync(v.job.p, &v.job_host, sizeof(DevJob), hipMemcpyHostToDevice, v.stream));
   if (pre_static) {
     launch_static(v.stream, same_profile(ctx->prof, default_profile_c()), (const DevJob*)v.job.p, ctx->prof, 1, 0,
                   ctx->staged_n, 0, (int)N, ctx->dc.n_keys);
@@ -4199,7 +4265,8 @@ static int svc_start_locked(kss_ctx* ctx) {
   v.npt = g.npt;
   v.bins_cap = bins_cap;
   v.cache_keys = cache_keys;
-  v.shmem = base + (cache_keys >= 0 ? node_cache_bytes(cap, cache_keys) : 0);
+  v.shmem = lds_cached;
+  v.shmem_nom = lds_cached + (v.simple ? 8 * (size_t)cap : 0);
   v.gen = std::max(need.bins_cap, 0) > 0 || need.general;
   ctx->last_geom[0] = g.W;
   ctx->last_geom[1] = g.threads;
@@ -4417,6 +4484,15 @@ static int svc_commit(kss_ctx* ctx, int32_t pod_index, int32_t node, int sign) {
     const double own = pod_index < (int)ctx->staged_bp.size() ? (double)ctx->staged_bp[pod_index].tlen : 0.0;
     ctx->count_bound += 1.0 + own;
     ctx->cell_bound += 1.0 + own;
+  }
+  if (sign > 0 && pod_index < (int)ctx->staged_uid.size()) {
+    // assume -> SchedulingQueue.DeleteNominatedPodIfExists, as kss_commit (the grid clears the
+    // entry's bit when it takes the command; a relaunch uploads the table without the entry)
+    const size_t before = ctx->nom.size();
+    const int32_t id = ctx->staged_uid[pod_index];
+    ctx->nom.erase(std::remove_if(ctx->nom.begin(), ctx->nom.end(), [&](const DevNom& e) { return e.pod == id; }),
+                   ctx->nom.end());
+    if (ctx->nom.size() != before) ctx->nom_dirty = true;
   }
   if (pod_index < (int)ctx->staged_bp.size())
     ctx->bound_log.push_back(BoundOp{local, sign > 0 ? 1 : 0, ctx->staged_bp[pod_index]});

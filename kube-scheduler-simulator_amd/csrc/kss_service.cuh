@@ -17,7 +17,9 @@
 //               compact record value did not fit); a SIMPLE grid (staged default-profile
 //               pods) runs svc_simple_eval instead: the k_simple chain, record rows stored
 //               from registers
-//     COMMIT / ROLLBACK   the owning shard applies AssumePod / ForgetPod (commit_pod)
+//     COMMIT / ROLLBACK   the owning shard applies AssumePod / ForgetPod (commit_pod); with a
+//               nominator (NOM grids) every shard also drops the committed pod's entry from its
+//               active mask (DeleteNominatedPodIfExists)
 //     STOP      leave (after writing the LDS node cache back)
 //
 // Every wait is bounded by wall time: shard 0 relays STOP after SVC_IDLE_TICKS without a
@@ -658,10 +660,42 @@ __device__ bool svc_window(long long* smem, Shard& S, bool plain, int K, int s0,
   return true;
 }
 
-template <bool COMPACT, bool INL>
+// The SIMPLE grid's view of the nominator (NOM instantiations, launched while the table is not
+// empty).  Entry j of the table lives in lane j of every wave, so one ballot turns a per-entry
+// predicate into the 64-bit entry mask (KSS_NOM_MAX = the wave size); `active` holds the entries
+// still nominated (an entry leaves with its pod's SVC_COMMIT: every shard takes every command, so
+// every shard clears the same bits), `here` per node slot of the shard the entries nominated to
+// that node (LDS behind the node cache, filled at every (re)launch from the uploaded table).
+struct SvcNom {
+  const DevNom* tab;
+  int n;
+  int node, prio, pod;  // this lane's entry (lane & 63); meaningful where `active` ever had its bit
+  uint64_t active;
+  const uint64_t* here;  // [cap]
+};
+
+__device__ __forceinline__ void svc_nom_load(SvcNom& sn, const DevJob& job, const Shard& S, int npt, uint64_t* here) {
+  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+  sn.tab = job.nom;
+  sn.n = min(job.n_nom, KSS_NOM_MAX);
+  sn.active = sn.n >= 64 ? ~0ull : ((1ull << sn.n) - 1ull);
+  const bool have = lane < sn.n;
+  sn.node = have ? job.nom[lane].node : -1;
+  sn.prio = have ? job.nom[lane].prio : 0;
+  sn.pod = have ? job.nom[lane].pod : 0;
+  for (int k = 0; k < npt; k++) {
+    const int n = S.lo + k * nt + tid;
+    uint64_t m = 0;
+    for (int j = 0; j < sn.n; j++) m |= (n < S.hi && job.nom[j].node == n) ? 1ull << j : 0ull;
+    here[k * nt + tid] = m;  // read back by this lane only
+  }
+  sn.here = here;
+}
+
+template <bool COMPACT, bool INL, bool NOM = false>
 __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const kss_profile& prof, int pi, long long* smem,
                                 Shard& S, int bins_cap, int npt, unsigned want, uint8_t* host, PodMeta& meta, bool plain,
-                                unsigned long long* st3) {
+                                unsigned long long* st3, const SvcNom* sn = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const size_t N = (size_t)c.N;
   const SlotLayout L(N);
@@ -714,9 +748,31 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     return true;
   }
   const uint32_t en = prof.filter_enabled;
+  // Nominated pods.  elig: the entries RunFilterPluginsWithNominatedPods adds for this pod wherever
+  // they are nominated (still nominated, priority at or above the pod's, not the pod itself:
+  // nom_here's conditions but the node, which sn->here[slot] supplies).  nom_m: the pod's own
+  // nominated node (PreferNominatedNode), -1 without one; the one-node list restarts the cursor.
+  uint64_t elig = 0;
+  int nom_m = -1;
+  int nom_out = -1;  // the owning lane: the nominated node's status where it lies outside the pod's list
+  if constexpr (NOM) {
+    const int self = pod_identity(p, job.pod_base + pi), prio = p.priority;
+    const bool act = (sn->active >> (tid & 63)) & 1ull;
+    elig = __ballot(act && sn->pod != self && sn->prio >= prio);
+    const uint64_t own = __ballot(act && sn->pod == self);
+    if (own) nom_m = __builtin_amdgcn_readlane(sn->node, 63 - __clzll((long long)own));
+    if (nom_m >= c.N) nom_m = -1;
+    if (nom_m >= 0) S.cursor = 0;
+  }
   // percentageOfNodesToScore < 100: the window from the cursor (svc_window)
   const int k_find = num_feasible_to_find(c.N, prof.pct_nodes_to_score);
   const bool win = k_find < c.N;
+  if constexpr (NOM) {
+    // without a window the whole list is processed: nextStartNodeIndex modulo the list's length
+    // (schedule_pod).  0 stays 0; only a failed evaluateNominatedNode outside a list (below)
+    // leaves another value at pct 100.
+    if (!win && p.names_len > 0) S.cursor = (int)((long long)S.cursor % p.names_len);
+  }
   const int s0 = win ? (int)(((long long)S.cursor % c.N + c.N) % c.N) : 0;
   uint32_t wu[6] = {0, 0, 0, 0, 0, 0};  // this lane's {Fa, TTa, NAa, Fb, TTb, NAb}
   long long nf = 0, max_tt = 0, max_na = 0;
@@ -743,10 +799,44 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     dr.nz[1] = (double)row.nz[1];
     dr.pods = row.pods;
     dr.allowed = row.allowed;
-    const SVal e = dyn_eval(prof, q, w, dr);
+    SVal e = dyn_eval(prof, q, w, dr);
     uint16_t detail = 0;
-    if (e.f == KSS_F_TAINT_TOLERATION || e.f == KSS_F_NODE_RESOURCES_FIT)
-      (void)filter_local(c, job.P, p, en, n, row, &detail);  // the failure's detail (taint id, fit bits)
+    bool first_failed = false, own_out = false;
+    int f1 = KSS_F_PASS;
+    if constexpr (NOM) {
+      // RunFilterPluginsWithNominatedPods' first pass on a node holding eligible nominees: the
+      // local chain on the row with their requests and pod count added, in int64 (filter_local:
+      // the f64 exactness bounds do not cover nominee sums).  Its failure is the node's verdict,
+      // detail bits from the augmented row; otherwise the plain pass below decides.  A pod of this
+      // chain has no ports, volumes, spread or inter-pod entries, so filter_chain is filter_local.
+      // A node outside the pod's NodeAffinity PreFilterResult list is never filtered, nominees or
+      // not (schedule_pod's restrict_names): its slot stays KSS_F_NOT_EVALUATED ...
+      const uint64_t here = sn->here[si] & elig;
+      // ... but evaluateNominatedNode filters the pod's own nominated node whatever the list
+      // says: both passes from filter_local (the static word holds no verdict for this node).
+      // The slot keeps KSS_F_NOT_EVALUATED for the full search; the status goes to nom_out.
+      own_out = n == nom_m && e.f == KSS_F_NOT_EVALUATED;
+      if (here && (own_out || e.f != KSS_F_NOT_EVALUATED)) {
+        uint16_t d1 = 0;
+        f1 = filter_local(c, job.P, p, en, n, row, &d1, sn->tab, here);
+        if (f1 != KSS_F_PASS) {
+          if (!own_out) e.f = f1;
+          detail = d1;
+          first_failed = true;
+        }
+      }
+    }
+    // the plain pass: the failure's detail (taint id, fit bits), or own_out's verdict
+    if (!first_failed && (own_out || e.f == KSS_F_TAINT_TOLERATION || e.f == KSS_F_NODE_RESOURCES_FIT)) {
+      const int f2 = filter_local(c, job.P, p, en, n, row, &detail);
+      if (own_out) f1 = f2;
+    }
+    if constexpr (NOM) {
+      if (own_out) {
+        nom_out = f1 | ((int)detail << 8);
+        detail = 0;
+      }
+    }
     sa.fail[si] = e.f | ((int)detail << 8);
     sa.tt[si] = e.tt;
     sa.na[si] = e.na;
@@ -763,6 +853,42 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     }
   }
   if (st3) st3[0] = wall_clock64();
+  // PreferNominatedNode (schedule_pod's evaluateNominatedNode): the nominated node's verdict is
+  // in its owner's slot already (the node pass above does not depend on the cursor, which the
+  // one-node list reset), or in nom_out where the node lies outside the pod's PreFilterResult
+  // list; one exchange tells every shard.  Feasible: the node is chosen without
+  // scoring and only it is recorded.  Otherwise its status stands in the record of the full
+  // search, which is the pass above from cursor 0.
+  bool nom_failed = false, nom_mine = false;
+  int nom_fw = 0;
+  if constexpr (NOM) {
+    if (nom_m >= 0) {
+      const int off = nom_m - S.lo;  // slot k * nt + tid of node S.lo + k * nt + tid
+      nom_mine = nom_m >= S.lo && nom_m < S.hi && off % nt == tid;
+      if (nom_mine) nom_fw = nom_out >= 0 ? nom_out : sa.fail[off];
+      long long v[1] = {(nom_mine && (nom_fw & 0xFF) == KSS_F_PASS) ? 1 : 0};
+      const int op[1] = {OP_MAX};
+      if (!svc_xchg<1, INL>(smem, S, plain, v, op)) return false;
+      if (v[0]) {
+        for (int k = 0; k < npt; k++) {
+          const int n = S.lo + k * nt + tid;
+          if (n >= S.hi) continue;
+          if (w_fail) svc_put<COMPACT>(host, o_fail, (size_t)n, 1, n == nom_m ? KSS_F_PASS : KSS_F_NOT_EVALUATED);
+          if (w_det) svc_put<COMPACT>(host, o_det, (size_t)n, 2, 0);
+          if (w_tot) svc_put<COMPACT>(host, o_tot, (size_t)n, es_tot, 0);
+#pragma unroll
+          for (int x = 0; x < KSS_NSCORE; x++) {
+            if (w_raw) svc_put<COMPACT>(host, o_raw, (size_t)x * N + n, es_raw, 0);
+            if (w_norm) svc_put<COMPACT>(host, o_norm, (size_t)x * N + n, es_norm, 0);
+          }
+        }
+        meta.n_feasible = 1;
+        meta.chosen = (int)(c.node_base + nom_m);
+        return true;
+      }
+      nom_failed = true;
+    }
+  }
   int wd = -1;  // the window's stopping node (-1: every node visited)
   if (win) {
     if (!svc_window(smem, S, plain, k_find, s0, sa, npt, wu, nf, max_tt, max_na, wd)) return false;
@@ -806,6 +932,9 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     const int pos = (n - s0 + c.N) % c.N;
     if (pos > pd) fw = KSS_F_NOT_EVALUATED;  // the search stopped before this node
     else if (pos == pd) fw = KSS_F_PASS | (KSS_PASS_NOT_KEPT << 8);  // the stopping node: filtered, dropped
+    if constexpr (NOM) {
+      if (nom_failed && nom_mine && n == nom_m) fw = nom_fw;  // evaluateNominatedNode's status stands
+    }
     const int f = fw & 0xFF;
     SVal e{f, sa.tt[si], (int)sa.na[si], sa.fit[si], sa.ba[si]};
     const bool pass = f == KSS_F_PASS && pos < pd;
@@ -846,6 +975,15 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     }
   }
   if (wd >= 0) S.cursor = wd;  // nextStartNodeIndex: the stopping node (every shard knows it)
+  if constexpr (NOM) {
+    // the nominated node's diagnosis entry counts once more unless the search (from 0) reached
+    // that node again: it lies behind the stopping node (uniform, no exchange)
+    if (nom_failed && wd >= 0 && nom_m > wd) S.cursor = (wd + 1) % c.N;
+    // ... or outside the pod's PreFilterResult list (no window on this chain then: the whole list
+    // was processed from 0, and the entry is one more; schedule_pod's nom_x over m_list)
+    if (nom_failed && wd < 0 && p.names_len > 0 && !in_names(job.P, p, (int64_t)c.node_base + nom_m))
+      S.cursor = 1 % p.names_len;
+  }
   meta.n_feasible = (int)nf;
   if (nf == 0) {
     meta.status = 1;
@@ -858,7 +996,7 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
   return true;
 }
 
-template <bool GEN, bool SIMPLE, bool INL = false>
+template <bool GEN, bool SIMPLE, bool INL = false, bool NOM = false>
 __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile& prof, int W, int npt, int bins_cap,
                              int cache_keys, unsigned long long* gran, int* err, SvcBox* box_flat,
                              unsigned long long* relay_flat, unsigned long long* seen_flat, uint8_t* rec_host,
@@ -909,6 +1047,17 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
   }
   if (threadIdx.x == 0) shdr(smem).svc_pf = -1;  // no prefetched pod (LDS holds garbage until written)
   __syncthreads();
+  // the nominator as uploaded for this launch (NOM: the table is not empty): every entry is
+  // nominated again -- the host removed the entries whose pods were assumed before it relaunched
+  SvcNom sn{};
+  uint64_t nom_active = 0;  // the general chain's NomView::active, kept across commands
+  if constexpr (NOM && SIMPLE) {
+    // (host: 8 bytes per slot behind the node cache, which a SIMPLE grid always has)
+    uint8_t* b = reinterpret_cast<uint8_t*>(xvec(smem) + NSCAL + bins_cap) + slot_arrays_bytes(cap);
+    svc_nom_load(sn, job, S, npt, reinterpret_cast<uint64_t*>(b + node_cache_bytes(cap, max(cache_keys, 0))));
+  } else if constexpr (NOM) {
+    nom_active = job.n_nom >= 64 ? ~0ull : ((1ull << job.n_nom) - 1ull);
+  }
   if (SIMPLE) svc_prefetch(job, smem, S, bins_cap, npt, 0);
   int* cmd = shdr(smem).cmd;
   if (w == 0 && threadIdx.x == 0) __hip_atomic_store(&box->running, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1005,9 +1154,9 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
       unsigned long long* sp3 = ((stamps & 1) && w == 0 && threadIdx.x == 0) ? st3 : nullptr;
       if (node & 2) S.cursor = cursor_prev;  // the same scheduling cycle again
       cursor_prev = S.cursor;
-      const bool ok = compact
-                          ? svc_simple_eval<true, INL>(c, job, prof, pi, smem, S, bins_cap, npt, want, crec_host, m, plain, sp3)
-                          : svc_simple_eval<false, INL>(c, job, prof, pi, smem, S, bins_cap, npt, want, rec_host, m, plain, sp3);
+      const bool ok =
+          compact ? svc_simple_eval<true, INL, NOM>(c, job, prof, pi, smem, S, bins_cap, npt, want, crec_host, m, plain, sp3, &sn)
+                  : svc_simple_eval<false, INL, NOM>(c, job, prof, pi, smem, S, bins_cap, npt, want, rec_host, m, plain, sp3, &sn);
       if (!ok) {
         if (threadIdx.x == 0) __hip_atomic_store(&box->err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         break;
@@ -1060,8 +1209,10 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
       PodMeta m;
       if (node & 2) S.cursor = cursor_prev;  // the same scheduling cycle again (the full record of a compact one)
       cursor_prev = S.cursor;
-      if (!schedule_pod<GEN>(c, job.P, prof, pi, smem, S, bins_cap, npt, &s, /*keep_norm=*/true, m,
-                             NomView{nullptr, 0, -1, 0})) {  // the host refuses the service while pods are nominated
+      // (without NOM the table is empty: the literal view lets every nominee path compile away)
+      const NomView nv = NOM ? NomView{job.nom, job.n_nom, pod_identity(job.P.pods[pi], job.pod_base + pi), nom_active}
+                             : NomView{nullptr, 0, -1, 0};
+      if (!schedule_pod<GEN>(c, job.P, prof, pi, smem, S, bins_cap, npt, &s, /*keep_norm=*/true, m, nv)) {
         if (threadIdx.x == 0) __hip_atomic_store(&box->err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         break;
       }
@@ -1109,6 +1260,17 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
         st_sys(&box->done[w], dv);
       }
     } else if (op == SVC_COMMIT || op == SVC_ROLLBACK) {
+      if constexpr (NOM) {  // assume -> DeleteNominatedPodIfExists: the same bits in every shard
+        if (op == SVC_COMMIT) {
+          const int id = pod_identity(job.P.pods[pi], job.pod_base + pi);
+          if constexpr (SIMPLE) {
+            sn.active &= ~__ballot(sn.pod == id);
+          } else {
+            for (int j = 0; j < job.n_nom; j++)
+              if (job.nom[j].pod == id) nom_active &= ~(1ull << j);
+          }
+        }
+      }
       const int local = node - c.node_base;
       if (threadIdx.x == 0 && local >= S.lo && local < S.hi)
         commit_pod(c, job.P, job.P.pods[pi], local, op == SVC_COMMIT ? 1 : -1);
