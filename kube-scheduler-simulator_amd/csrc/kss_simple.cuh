@@ -2342,12 +2342,39 @@ __device__ __forceinline__ bool simple_sync_flat(SimpleHdr& H, int& parity, long
 //   after the closing barrier, the wave that owns the winner's slot commits pod k on its row and
 //                        copies pnd[that wave][c] to T[c][slot].
 // Invariant: after pod k's commit and copy, T[c][s] is the evaluation on the committed state.
+// Staging.  No LDS read stands between the exchange's result and pass B, and one between the
+// wave's candidate and its statistics: in pod k's exchange window (the idle hook: after the
+// statistics barrier, waves 1.. after their refresh jobs, wave 0 ahead of its sweep) every lane
+// loads what iteration k+1 reads of its own slot -- T[shape(k+1)][s], T[shape(k+2)][s], the
+// static words of pods k+1 and k+2 -- and the wave-uniform record fields (status, creq of pod
+// k+1; flags, fit_req of pod k+2) into registers.  After the closing barrier the winner x is
+// known: the lane of slot x takes pnd[its wave][shape(k+1)] and pnd[its wave][shape(k+2)] for its
+// two table words, exactly what the column copy writes into T; every other staged value is of a
+// slot or record pod k's commit does not touch.  Statistics: the lanes select from registers, and
+// lane pwv alone reads its candidate's row and static word, as one group of independent loads.
+// Every reduction runs where it did, on the same values.  The first iteration of a launch stages
+// from the prologue's table.
 // Ordering.  A slot's T entries and, between the barriers below, its row are written by the
 // wave that owns the slot only, and T is read by that wave only: program order.  The rows are
 // read by other waves in the refresh, between the statistics barrier and the closing barrier
 // of a pod, and written (the commit) between the closing barrier and the next statistics
 // barrier; pnd is written in the first interval and read in the second.  (So the commit is not
 // wave 0's, before the closing barrier, as in simple_sync_pw's own: commit = false there.)
+// Pod k's commit and column copy are the owner wave's, right behind the winner lane's two pnd
+// reads: between pod k's closing barrier and pod k+1's statistics barrier as before, in program
+// order before that wave's lane pwv reads its candidate's row (the candidate may be x) and before
+// the wave's staging loads of T in window k+1.  Pass B of pod k+1 reads no LDS, so it does not wait
+// for them.  (Moving them behind the key reduction of pod k+1 was measured and lost 3 %:
+// profiles/r14a_table_staging_ab.txt.)
+// Rings.  The prefetch wave stores record and static words of pod k + PD in window k (ring slot
+// (k - 1) % RING, whose last readers, pod k-1's refresh and commit, are behind a barrier)
+// and only then issues the loads of pod k + PD + 1, which it stores one window later: the HBM
+// loads no longer stand in front of that wave's publish.  A ring slot is therefore visible from
+// the closing barrier of window (pod - PD) on, as before: window k reads the slots of pods k+1
+// and k+2 (the staging; the shape of pod k+2 is read at the top of iteration k), stored in windows
+// k-2 and k-1 at the latest and each behind a closing barrier; the slot window k itself writes is
+// neither.  Window k0 - 1
+// loads pod k0 + PD, the first one the prologue did not.
 // FLAT (k_simple_tab_flat): the per-pod reduction and exchange is simple_sync_flat instead of
 // simple_sync_pw; the waves' candidates in H.red, the two barriers and everything between them
 // are the same, so the ordering above holds for both.
@@ -2362,7 +2389,9 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
                                                     unsigned long long* gran, const XPeers& X, unsigned epoch0, int* err,
                                                     unsigned long long* stamps, long long* smem, int n_shapes) {
   constexpr kss_profile prof = default_profile_c();
-  constexpr int PD = 3;  // prefetch distance of per-wave mode (simple_schedule)
+  constexpr int PD = 3;  // prefetch distance of per-wave mode (simple_schedule): window k stores pod k + PD
+  constexpr int PD_TAB = PD + 1;  // ... and loads pod k + PD_TAB, carried one iteration in registers
+  static_assert(PD_TAB == RING, "window k stores ring slot (k - 1) % RING: no reader left (see Staging)");
   constexpr int NQ = (int)(sizeof(SPod) / 16);
   const int tid = threadIdx.x, nt = blockDim.x;
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
@@ -2459,14 +2488,38 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
   const int idle_n = 64 * (nwave - 1), jobs = nwave * n_shapes;
   const int job0 = tid - 64;  // (waves 1.. only)
   const int v0 = job0 >= 0 ? job0 / n_shapes : 0, j0 = job0 >= 0 ? job0 % n_shapes : 0;
-  // the shapes of pods k, k+1 (and k+2, read one pod ahead of its use)
-  int ck = 0, cn = min(max(L.ring[k0 % RING].shape, 0), n_shapes - 1), cnn = 0;
+  // the shapes of pods k+1 and k+2
+  int cn = min(max(L.ring[k0 % RING].shape, 0), n_shapes - 1), cnn = 0;
   // the flat exchange: the nodes of the entries this lane holds in the sweep (simple_sync_flat)
   uint32_t er[SXF_LOADS] = {};
   if constexpr (FLAT) {
 #pragma unroll
     for (int i = 0; i < SXF_LOADS; i++) er[i] = flat_entry_range(i * 16 + (lane >> 2), per, c.N, W, nwave);
   }
+  // the staged operands of iteration kk (pods kk and kk + 1 of shapes ca, cb): see "Staging" above
+  uint32_t sa_t = 0, sa_w = 0, sb_t = 0, sb_w = 0;
+  int32_t s_status = 0, s_flags = 0;
+  double s_creq[3] = {0.0, 0.0, 0.0}, s_fit[3] = {0.0, 0.0, 0.0};
+  // Loads only, all independent and none conditional, so that a wave issues them and goes on
+  // (wave 0 to its sweep) without waiting: a lane that owns no slot reads slot 0 and a pod outside
+  // [k0, k1) whatever its ring slot holds; `mine`, k >= k0 and k + 1 < k1 are applied where the
+  // values are used.
+  const int ss = mine ? s : 0;
+  auto stage = [&](int kk, int ca, int cb) {
+    const int ra = (kk + RING) % RING, rb = (kk + 1) % RING;
+    sa_t = TB.T[ca * TB.ts + ss];
+    sa_w = L.st[ra * cap + ss];
+    sb_t = TB.T[cb * TB.ts + ss];
+    sb_w = L.st[rb * cap + ss];
+    s_status = L.ring[ra].status;
+    s_flags = L.ring[rb].flags;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      s_creq[i] = L.ring[ra].creq[i];
+      s_fit[i] = L.ring[rb].fit_req[i];
+    }
+  };
+  stage(k0 - 1, 0, cn);  // the first iteration has no earlier window: from the prologue's table
   for (int k = k0 - 1; k < k1; k++) {
     KSS_GLOBAL unsigned long long* sp = (stamps && k >= k0 && k - k0 < KSS_NSTAMP_PODS / 2)
                                             ? gstamps + (size_t)w * 8 * KSS_NSTAMP_PODS + (size_t)(k - k0) * 16
@@ -2474,65 +2527,68 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
     if (sp && tid == 0) sp[0] = wall_clock64();
     if (sp && tid == 64) sp[9] = wall_clock64();
     const SPod& pk = L.ring[(k + RING) % RING];
-    const SPod& qn = L.ring[(k + 1) % RING];
-    const int slk = (k + RING) % RING, sln = (k + 1) % RING;
+    const int sln = (k + 1) % RING;
+    // (pod k+2's record: stored in window k - 1 at the latest, behind its closing barrier)
     if (k + 2 < k1) cnn = min(max(L.ring[(k + 2) % RING].shape, 0), n_shapes - 1);
-    const bool pf_on = pf_wave && k >= k0 && k + PD < k1 && own > 0;
-    if (pf_on) {
-      KSS_GLOBAL const uint4& src = gspod[(size_t)(k + PD) * NQ + min(pf_lane, NQ - 1)];
-      pfq = make_uint4(src.x, src.y, src.z, src.w);
-#pragma unroll
-      for (int j = 0; j < PF_MAX; j++)
-        if (j < pf_per) pfw[j] = ld_ag(&gstat[(size_t)(k + PD - k0) * N + lo + min(j * pf_n + pf_lane, own - 1)]);
-    }
+    // the prefetch wave: record and static words of pod k + PD_TAB are loaded in pod k's exchange
+    // window and stored into their ring slots in pod k + 1's
+    const bool pf_ld = pf_wave && k + PD_TAB < k1 && own > 0;
+    const bool pf_st = pf_wave && k >= k0 && k + PD < k1 && own > 0;  // (what window k - 1 loaded)
     const bool refresh_on = k >= k0 && k + 1 < k1;  // pod k may commit and a pod after it reads the table
-    // pass B: pod k's values from the table and its static word
+    // this iteration's operands leave the staging registers (the window below refills them)
+    const uint32_t a_t = sa_t, a_w = sa_w, b_t = sb_t, b_w = sb_w;
+    const int32_t k_status = s_status, n_flags = s_flags;
+    const double k_creq[3] = {s_creq[0], s_creq[1], s_creq[2]}, n_fit[3] = {s_fit[0], s_fit[1], s_fit[2]};
+    // pass B: pod k's table word and static word (staged), arithmetic on registers
     const long long nf = R[1];
     const int max_tt = (int)R[2], max_na = (int)R[3];
     const bool scored = nf > 1;
-    const bool keys = k >= k0 && pk.status == 0 && nf > 0;
+    const bool keys = k >= k0 && k_status == 0 && nf > 0;
     const float rtt = __builtin_amdgcn_rcpf((float)max(max_tt, 1));
     const float rna = __builtin_amdgcn_rcpf((float)max(max_na, 1));
     long long best = 0;
-    if (keys && mine) {
-      const uint32_t t = TB.T[ck * TB.ts + s], wd = L.st[slk * cap + s];
-      const SVal e{sw_code(wd), sw_tt(wd), sw_na(wd), (int)((t >> 8) & 0xFFu), (int)(t & 0xFFu)};
+    {
+      const SVal e{sw_code(a_w), sw_tt(a_w), sw_na(a_w), (int)((a_t >> 8) & 0xFFu), (int)(a_t & 0xFFu)};
       const long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s));
-      best = (e.f == 0 && (t & ST_FITS)) ? key : 0;
+      best = (keys && mine && e.f == 0 && (a_t & ST_FITS)) ? key : 0;
     }
     if (sp && tid == 0) sp[1] = wall_clock64();
     best = wave_max_key(best, kb, c.node_base);
     if (sp && tid == 0) sp[2] = wall_clock64();
     const int cand = best ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)best) - c.node_base - lo : -1;
-    // statistics of pod k+1: H0 from the table; H1 on the wave's candidate with pod k added
+    // statistics of pod k+1: H0 from the staged table word; H1 on the wave's candidate with pod k
+    // added, whose row and static word lane pwv alone reads (one group of independent loads)
     uint32_t u[6] = {0, 0, 0, 0, 0, 0};
     if (k + 1 < k1) {
       const bool extra = lane == pwv && cand >= 0;
-      if (mine || extra) {
-        const int ns = extra ? cand : s;
-        const uint32_t wd = L.st[sln * cap + ns];
-        bool ok;
-        if (extra) {  // fitsRequest of pod k+1 on the row after AssumePod(pod k): the verdict alone
-          bool bad = (int64_t)L.r32[ns] + 2 > (int64_t)L.r32[cap + ns];
-          bool sh = false;
+      bool ok = mine && (b_t & ST_FITS) != 0;
+      uint32_t wd = b_w;
+      if (extra) {  // fitsRequest of pod k+1 on the row after AssumePod(pod k): the verdict alone
+        const int ns = cand;
+        wd = L.st[sln * cap + ns];
+        const int32_t pods = L.r32[ns], allowed = L.r32[cap + ns];
+        double al[3], rq[3];
 #pragma unroll
-          for (int i = 0; i < 3; i++)
-            sh |= qn.fit_req[i] > L.r64[i * cap + ns] - (L.r64[(3 + i) * cap + ns] + pk.creq[i]);
-          bad |= !(qn.flags & SP_ALLZERO) & sh;
-          ok = !bad;
-        } else {
-          ok = (TB.T[cn * TB.ts + s] & ST_FITS) != 0;
+        for (int i = 0; i < 3; i++) {
+          al[i] = L.r64[i * cap + ns];
+          rq[i] = L.r64[(3 + i) * cap + ns];
         }
-        ok &= sw_code(wd) == 0;
-        const bool c0 = ok && !extra, c1 = ok && (extra || s != cand);
-        const uint32_t tt = (uint32_t)sw_tt(wd), na = (uint32_t)sw_na(wd);
-        u[0] = c0 ? 1u : 0u;
-        u[1] = c0 ? tt : 0u;
-        u[2] = c0 ? na : 0u;
-        u[3] = c1 ? 1u : 0u;
-        u[4] = c1 ? tt : 0u;
-        u[5] = c1 ? na : 0u;
+        bool bad = (int64_t)pods + 2 > (int64_t)allowed;
+        bool sh = false;
+#pragma unroll
+        for (int i = 0; i < 3; i++) sh |= n_fit[i] > al[i] - (rq[i] + k_creq[i]);
+        bad |= !(n_flags & SP_ALLZERO) & sh;
+        ok = !bad;
       }
+      ok &= sw_code(wd) == 0;
+      const bool c0 = ok && !extra, c1 = ok && (extra || s != cand);
+      const uint32_t tt = (uint32_t)sw_tt(wd), na = (uint32_t)sw_na(wd);
+      u[0] = c0 ? 1u : 0u;
+      u[1] = c0 ? tt : 0u;
+      u[2] = c0 ? na : 0u;
+      u[3] = c1 ? 1u : 0u;
+      u[4] = c1 ? tt : 0u;
+      u[5] = c1 ? na : 0u;
     }
     if (sp && tid == 0) sp[3] = wall_clock64();
     auto idle = [&]() {
@@ -2550,11 +2606,20 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
         }
         if (sp && (tid == 64 || tid == 128)) sp[11 + (tid >> 6)] = wall_clock64();  // waves 1, 2: refresh done
       }
-      if (pf_on) {  // the prefetched record and static words -> their ring slots (simple_schedule)
+      // the operands of pod k + 1's iteration (every wave; wave 0 issues them ahead of its sweep)
+      stage(k + 1, cn, cnn);
+      if (pf_st) {  // the record and static words loaded one window ago -> their ring slots
         reinterpret_cast<uint4*>(L.ring + (k + PD) % RING)[min(pf_lane, NQ - 1)] = pfq;
 #pragma unroll
         for (int j = 0; j < PF_MAX; j++)
           if (j < pf_per) L.st[((k + PD) % RING) * cap + min(j * pf_n + pf_lane, own - 1)] = pfw[j];
+      }
+      if (pf_ld) {  // ... and the next ones, behind this wave's publish
+        KSS_GLOBAL const uint4& src = gspod[(size_t)(k + PD_TAB) * NQ + min(pf_lane, NQ - 1)];
+        pfq = make_uint4(src.x, src.y, src.z, src.w);
+#pragma unroll
+        for (int j = 0; j < PF_MAX; j++)
+          if (j < pf_per) pfw[j] = ld_ag(&gstat[(size_t)(k + PD_TAB - k0) * N + lo + min(j * pf_n + pf_lane, own - 1)]);
       }
       if (tid == out_tid) store_pending();  // the previous pod's outcome
     };
@@ -2569,8 +2634,14 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
     if (k >= k0) {
       const long long K = R[0];
       const int x = K ? (int)(0xFFFFFFFFu - (uint32_t)(unsigned long long)K) - c.node_base : -1;
-      // the wave that owns the winner's slot: AssumePod on its row, the pending row into the table
+      // the wave that owns the winner's slot: the winner's lane takes the pending values of pods
+      // k+1 and k+2 (what its next pass B waits for), then AssumePod on the row and the pending row
+      // into the table -- LDS traffic that pass B, register arithmetic, no longer waits behind
       if (x >= lo && x < hi && (x - lo) / max(pwv, 1) == wv) {
+        if (refresh_on && s == x - lo) {
+          sa_t = TB.pnd[wv * KSS_MAX_SHAPES + cn];
+          sb_t = TB.pnd[wv * KSS_MAX_SHAPES + cnn];
+        }
         simple_commit_lanes(L, pk, x - lo, lane);
         if (refresh_on && lane < n_shapes) TB.T[lane * TB.ts + (x - lo)] = TB.pnd[wv * KSS_MAX_SHAPES + lane];
       }
@@ -2578,12 +2649,11 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
         pend.chosen = K ? x + c.node_base : -1;
         pend.n_feasible = (int)nf;
         pend.scored = (K && scored) ? 1 : 0;
-        pend.status = pk.status != 0 ? (pk.status == KSS_PF_ERROR ? 3 : 2) : (nf == 0 ? 1 : 0);
+        pend.status = k_status != 0 ? (k_status == KSS_PF_ERROR ? 3 : 2) : (nf == 0 ? 1 : 0);
         pend.best_total = pend.scored ? (int64_t)((unsigned long long)K >> 32) : 0;
         pend_k = k;
       }
     }
-    ck = cn;
     cn = cnn;
     if (sp && tid == 0) sp[6] = wall_clock64();
   }
