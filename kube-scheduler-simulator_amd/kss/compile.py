@@ -419,6 +419,11 @@ class CompiledCluster:
     def n_nodes(self) -> int:
         return len(self.node_names)
 
+    @property
+    def port_index(self) -> Dict[Tuple[str, str, int], int]:
+        """(ip, protocol, port) -> its bit in port_used / kss_boundset.ports / port_add."""
+        return {e: i for i, e in enumerate(self.ports)}
+
     def as_struct(self, node_base: int = 0) -> abi.Cluster:
         a = self.arrays
         c = abi.Cluster()
