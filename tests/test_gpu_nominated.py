@@ -22,6 +22,7 @@ import k8s_oracle as ko
 import k8s_preemption as kp
 import nominated_fixtures as nf
 import oracle_c
+import preempt_compare as pc
 import preempt_fixtures as pf
 from kss import abi, native, synth
 from kss.compile import compile_cluster
@@ -172,8 +173,7 @@ def _oracle_seq(nodes, bound, pods):
         if r["selected"] is not None:
             res.append((j, "scheduled", ko._name(o.nodes[r["selected"]]), []))
         else:
-            nom = ko._name(o.nodes[pre["nominated"]]) if pre["nominated"] is not None else None
-            res.append((j, pre["status"], nom, [v[1] for v in pre["victims"]]))
+            res.append((j,) + pc.from_python(o, pre))  # the full tuple: counts and criteria included
     return res
 
 
@@ -183,9 +183,6 @@ def _device_seq(nodes, bound, pods):
     ctx = _ctx(cc)
     ctx.load_bound(cc.as_boundset())
     prio = [ko.pod_priority(p) for p in pods]
-
-    def victim_name(v):
-        return cc.bound_names[v][1] if v >= 0 else cp.names[-1 - v][1]
 
     queue, tries, out = list(range(cp.n)), [0] * cp.n, []
     while queue:
@@ -197,8 +194,7 @@ def _device_seq(nodes, bound, pods):
             continue
         pre = ctx.postfilter_pod(ps, j)
         st = STATUS[pre["status"]]
-        nom = cc.node_names[pre["nominated"]] if pre["nominated"] >= 0 else None
-        out.append((j, st, nom, [victim_name(v) for v in pre["victims"]]))
+        out.append((j,) + pc.from_native(pre, cc, cp))
         if st == "nominated":
             node = pre["nominated"]
             ctx.remove_bound(pre["victims"])  # prepareCandidate deletes them; the informer removes them

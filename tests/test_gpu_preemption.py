@@ -1,6 +1,8 @@
 """DefaultPreemption PostFilter dry run on the device (k_preempt through kss_postfilter_pod)
-against the object-level restatement (oracle/k8s_preemption.py): status, nominated node and
-the victims in eviction order for every unschedulable pod of a sequence -- the hand-derived
+against the object-level restatement (oracle/k8s_preemption.py): the full tuple of
+tests/preempt_compare.py (status, nominated node, the victims in eviction order, the potential
+and candidate counts, the victim count and the nominated node's pickOneNodeForPreemption
+criteria) for every unschedulable pod of a sequence -- the hand-derived
 fixture and seeded saturated clusters (every node nearly full of pods of mixed priority),
 with the pods placed earlier in the sequence (per-pod commits or a batch) as potential
 victims."""
@@ -8,14 +10,12 @@ import pytest
 
 import k8s_oracle as ko
 import k8s_preemption as kp
+import preempt_compare as pc
 import preempt_fixtures as pf
 from kss import abi, native
 from kss.compile import compile_cluster
 
 pytestmark = pytest.mark.gpu
-
-STATUS = {abi.KSS_PREEMPT_NOMINATED: "nominated", abi.KSS_PREEMPT_NO_CANDIDATE: "no_candidate",
-          abi.KSS_PREEMPT_NOT_ELIGIBLE: "not_eligible", abi.KSS_PREEMPT_SCHEDULABLE: "schedulable"}
 
 
 def _oracle(nodes, bound, pods):
@@ -25,8 +25,7 @@ def _oracle(nodes, bound, pods):
         if r["selected"] is not None:
             res.append(("scheduled", ko._name(o.nodes[r["selected"]]), []))
         else:
-            nom = ko._name(o.nodes[pre["nominated"]]) if pre["nominated"] is not None else None
-            res.append((pre["status"], nom, [v[1] for v in pre["victims"]]))
+            res.append(pc.from_python(o, pre))  # the full tuple: counts and criteria included
     return res
 
 
@@ -37,9 +36,6 @@ def _device(nodes, bound, pods, batch_first=0):
     ctx.load(cc.as_struct(), names=native.make_names(cc.node_names, cc.taints, cc.scalars))
     bs = cc.as_boundset()
     ctx.load_bound(bs)
-
-    def victim_name(v):
-        return cc.bound_names[v][1] if v >= 0 else cp.names[-1 - v][1]
 
     out = []
     if batch_first:
@@ -57,15 +53,16 @@ def _device(nodes, bound, pods, batch_first=0):
             continue
         pre = ctx.postfilter_pod(ps, j)
         assert pre["n_victims"] == len(pre["victims"])
-        nom = cc.node_names[pre["nominated"]] if pre["nominated"] >= 0 else None
-        out.append((STATUS[pre["status"]], nom, [victim_name(v) for v in pre["victims"]]))
+        out.append(pc.from_native(pre, cc, cp))
     ctx.close()
     return out
 
 
 def test_hand_derived_fixture_on_device():
     nodes, bound, pods, expect = pf.fixture()
-    assert _device(nodes, bound, pods) == [tuple(e) for e in expect]
+    got = _device(nodes, bound, pods)
+    assert [g[:3] for g in got] == [tuple(e) for e in expect]
+    assert got == _oracle(nodes, bound, pods)  # nothing schedules: the full tuples of the same dry runs
 
 
 @pytest.mark.parametrize("seed,n_nodes,n_pods", [(1, 60, 40), (2, 60, 40), (3, 200, 60), (4, 500, 60)])

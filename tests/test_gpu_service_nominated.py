@@ -14,6 +14,7 @@ import pytest
 import k8s_oracle as ko
 import nominated_fixtures as nf
 import oracle_c
+import preempt_compare as pc
 import preempt_fixtures as pf
 import test_gpu_nominated as tgn
 import volume_fuzz
@@ -372,9 +373,6 @@ def _service_seq(nodes, bound, pods):
     ctx.stage(ps)
     prio = [ko.pod_priority(p) for p in pods]
 
-    def victim_name(v):
-        return cc.bound_names[v][1] if v >= 0 else cp.names[-1 - v][1]
-
     queue, tries, out = list(range(cp.n)), [0] * cp.n, []
     while queue:
         j = queue.pop(0)
@@ -385,8 +383,7 @@ def _service_seq(nodes, bound, pods):
             continue
         pre = ctx.postfilter_pod(ps, j)
         st = tgn.STATUS[pre["status"]]
-        nom = cc.node_names[pre["nominated"]] if pre["nominated"] >= 0 else None
-        out.append((j, st, nom, [victim_name(v) for v in pre["victims"]]))
+        out.append((j,) + pc.from_native(pre, cc, cp))  # the full tuple, as test_gpu_nominated._device_seq
         if st == "nominated":
             node = pre["nominated"]
             ctx.remove_bound(pre["victims"])

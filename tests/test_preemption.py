@@ -8,6 +8,7 @@ import pytest
 
 import k8s_oracle as ko
 import k8s_preemption as kp
+import preempt_compare as pc
 import preempt_fixtures as pf
 from kss import abi
 from kss.compile import compile_cluster
@@ -80,22 +81,14 @@ STATUS = {abi.KSS_PREEMPT_NOMINATED: "nominated", abi.KSS_PREEMPT_NO_CANDIDATE: 
 
 def _c_dry_runs(nodes, bound, pods, threads, nominations=()):
     """The C restatement (oracle/kss_oracle.c kss_oracle_postfilter) of every pod against the
-    initial snapshot (nothing committed), as (status, nominated node, victims, criteria).
+    initial snapshot (nothing committed), as preempt_compare's full tuple (status, nominated
+    node, victims, the two counts and the nominated node's three criteria).
     nominations: [(pod index, node index)] in the nominator."""
     import oracle_c
     cc, cp, _ = compile_cluster(nodes, bound, pods)
     cl, ps, bs = cc.as_struct(), cp.as_struct(), cc.as_boundset()
-
-    def victim(v):
-        return cc.bound_names[v][1]
-
-    out = []
-    for j in range(cp.n):
-        r = oracle_c.postfilter(abi.default_profile(), cl, ps, j, bs, threads=threads, nominations=nominations)
-        nom = cc.node_names[r["nominated"]] if r["nominated"] >= 0 else None
-        out.append((STATUS[r["status"]], nom, [victim(v) for v in r["victims"]],
-                    (r["n_potential"], r["n_candidates"])))
-    return out
+    return [pc.from_native(oracle_c.postfilter(abi.default_profile(), cl, ps, j, bs, threads=threads,
+                                               nominations=nominations), cc, cp) for j in range(cp.n)]
 
 
 def _py_dry_runs(nodes, bound, pods, nominations=()):
@@ -105,9 +98,7 @@ def _py_dry_runs(nodes, bound, pods, nominations=()):
     out = []
     for p in pods:
         r = o.schedule_one(p, commit=False)
-        pre = kp.preempt(o, p, r)
-        nom = ko._name(o.nodes[pre["nominated"]]) if pre["nominated"] is not None else None
-        out.append((pre["status"], nom, [v[1] for v in pre["victims"]], (pre["n_potential"], pre["n_candidates"])))
+        out.append(pc.from_python(o, kp.preempt(o, p, r)))
     return out
 
 
@@ -125,8 +116,9 @@ def test_c_postfilter_matches_hand_derived():
 
 @pytest.mark.parametrize("seed,n_nodes,n_pods,threads", [(1, 60, 40, 1), (2, 60, 40, 4), (3, 200, 60, 8)])
 def test_c_postfilter_matches_object_oracle(seed, n_nodes, n_pods, threads):
-    """Saturated clusters: status, nominated node, victims in eviction order and the
-    potential / candidate counts equal the object-level restatement, at any thread count."""
+    """Saturated clusters: status, nominated node, victims in eviction order, the potential /
+    candidate counts and the nominated node's criteria (highest victim priority, priority sum,
+    earliest start) equal the object-level restatement, at any thread count."""
     nodes, bound, pods = pf.saturated(seed, n_nodes, n_pods)
     got = _c_dry_runs(nodes, bound, pods, threads)
     want = _py_dry_runs(nodes, bound, pods)
