@@ -459,7 +459,11 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * "coop_launch", "service_general", "service_stamps", "svc_xcd", "svc_no_static", "svc_full_fence",
  * "svc_inline_sweep", "svc_huge", "service_no_diff", "sweep_pipe", "axis_blocks", "axis_no_fold",
  * "trace_path", "xcd_force_fallback" (XCD-local launches report failed placement, so the
- * unrestricted rerun runs: tests).  Read when a context is created (shards, xcd, xcd_shards,
+ * unrestricted rerun runs: tests), "simple_ports_images" (default 0; 1: a staged, unrecorded batch
+ * without spread / inter-pod programs and without volumes whose pods hold host ports (NodePorts) or
+ * node-cached images (ImageLocality) runs on k_simple's ports-and-images form instead of
+ * k_schedule, on one part, provided every pod's preferred NodeAffinity weights sum to at most 8191;
+ * batches without such pods are routed as with 0; kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -911,7 +915,13 @@ int kss_abi_sizes(int32_t* out, int32_t n);
 /* Host only (no device): which sequential-loop kernel a staged, unrecorded batch of `ps` on
  * `cl` can take, by its pod programs: out3[0] = 1 k_simple, 2 k_spread, 0 k_schedule only;
  * out3[1] = the first pod that rules out k_spread (-1 none), out3[2] = the reason code
- * (kss_plan_reason).  The launch still checks LDS geometry and value bounds. */
+ * (kss_plan_reason).  The launch still checks LDS geometry and value bounds.
+ * Pods with host ports or node-cached images: k_schedule only (reason "host ports (NodePorts),
+ * ..."), unless the process-wide option "simple_ports_images" is 1; then the batch is planned on
+ * k_simple (its ports-and-images form) when it has no spread / inter-pod program and no volume and
+ * every pod's Σ positive preferred NodeAffinity weights is <= 8191 (else k_schedule: the volume
+ * pod's reason as before, or the reason naming the 8191 limit and its pod).  k_spread, sweeps, the
+ * split grid, the node axis and the service grid refuse such pods whatever the option says. */
 int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3);
 /* The same with the profile the batch runs under (NULL: kss_plan_podset): a profile with
  * percentageOfNodesToScore below 100 on a cluster of 100+ nodes (the findNodesThatPassFilters

@@ -77,7 +77,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_N
 };
 struct OptDef {
   const char* name;
@@ -115,6 +115,7 @@ const OptDef kOptDefs[O_N] = {
     {"spread_lb256", "KSS_SPREAD_LB256", 1},              // k_spread compiled for <= 256 lanes when the shard fits
     {"shape_table", "KSS_SHAPE_TABLE", 1},                // k_simple's shape table: 1 sharded grids that admit it, 2 also one shard, 0 never
     {"flat_exchange", "KSS_FLAT_EXCHANGE", 1},            // the shape-table loop's exchange: 1 every wave publishes (one sweep), 0 two-level
+    {"simple_ports_images", "KSS_SIMPLE_PORTS_IMAGES", 0},  // k_simple's ports-and-images form for NodePorts / ImageLocality pods
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -355,6 +356,42 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple(const DevJob* __rest
                                      P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor);
 }
 
+// k_simple's ports-and-images form (simple_schedule<.., PI = true>): pods with host ports
+// (NodePorts: the UsedPorts column in LDS) and node-cached images (ImageLocality: in the static
+// word, k_static_pi).  Kernels of their own with k_simple's argument list, launched only for
+// a batch that holds such a pod (kss_set_option "simple_ports_images"), so k_simple keeps its code.
+// sports: the pods' NodePorts masks [n_pods] of the one job, a trailing argument of its own (DevJob
+// does not grow: every kernel copies it).
+template <bool DEF, bool WIN>
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_pi(const DevJob* __restrict__ jobs, kss_profile prof, int W,
+                                                               int cap, int k0, int k1, unsigned long long* gran, int* err,
+                                                               unsigned long long* stamps, XPeers X, unsigned epoch0,
+                                                               int stat_row0, int k_find, const SPort* sports) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const int Wl = X.n > 1 ? X.wl : W;
+  auto ctr_off = [&] { return WIN ? 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 : 2 * (size_t)W * SX_VALS; };
+  int xs = 0;  // as k_simple
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, ctr_off, W, err)) < 0) return;
+  const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
+  const DevJob job = jobs[ji];
+  constexpr kss_profile def_prof = default_profile_c();
+  if (!DEF) stage_profile(H, jobs[ji].prof);
+  const kss_profile& P = DEF ? def_prof : H.prof;
+  const int per = (job.c.N + W - 1) / W, nwave = (int)(blockDim.x >> 6);
+  unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
+  unsigned long long* sp = ji == 0 ? stamps : nullptr;
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  if (per <= PW_LANES * nwave)
+    simple_schedule<DEF, true, WIN, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                          job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                          sports);
+  else
+    simple_schedule<DEF, false, WIN, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                           job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                           sports);
+}
+
 // k_simple<true, false> in per-wave mode with the shape table (simple_schedule_tab): a kernel of
 // its own, so the kernels above keep their register allocation.  Same arguments (launch_simple
 // passes one argument list); n_shapes takes k_find's place.  The host launches it only for a
@@ -501,6 +538,98 @@ __global__ __launch_bounds__(256) void k_static(const DevJob* __restrict__ jobs,
                       const int ni = n + min(i, cnt - 1);
                       return c.ncl ? label_of(c, key, ni) : gp(c.label_value)[(size_t)key * N + ni];
                     }, w);
+    uint32_t* dst = &stat[(size_t)(row0 + k - k0) * N + n];  // row0: the half of a double-buffered table
+    if (quad) {
+      st_ag16(dst, kss_u32x4{w[0], w[1], w[2], w[3]});
+    } else if (pair) {
+      if (cnt >= 2) st_ag(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)w[0] | ((unsigned long long)w[1] << 32));
+      else st_ag(dst, w[0]);
+      if (cnt == 4) st_ag(reinterpret_cast<unsigned long long*>(dst + 2), (unsigned long long)w[2] | ((unsigned long long)w[3] << 32));
+      else if (cnt == 3) st_ag(dst + 2, w[2]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        if (i < cnt) st_ag(dst + i, w[i]);
+    }
+  }
+  // every store above is agent-scope (sc1, written through): the kernel boundary orders them
+  // for the loop kernel's agent-scope loads, no L2 write-back per wave (C5: 256k workgroups,
+  // an agent release in each cost 9 ms per sweep step)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// k_static for the ports-and-images form of the word (kss_simple.cuh SWPI_*; k_simple_pi reads it):
+// NodeAffinity in 13 bits, the pod's ImageLocality score on the node above it.  The image rows
+// ints[img_off ..] are read like the rest of the program, through the constant address space
+// (wave-uniform: scalar loads).  A kernel of its own that restates k_static's body: sharing the body
+// as an inline function changed k_static's register allocation.  A change to one is made in both.
+template <bool DEF>
+__global__ __launch_bounds__(256) void k_static_pi(const DevJob* __restrict__ jobs, kss_profile prof_arg, int k0, int k1,
+                                                   int n_lo, int n_hi, int lkeys, int row0, int ppb) {
+  extern __shared__ int32_t slab[];  // [lkeys][1024]
+  const DevJob& job = jobs[blockIdx.z];
+  const int N = job.c.N;
+  const int nb = n_lo + 4 * (int)(blockIdx.x * 256);  // the block's first node
+  const int n = nb + 4 * (int)threadIdx.x;  // rows [n_lo, min(n_hi, N)): a split grid's own rows
+  const int kend = min(k1, job.n_pods);
+  const int kb = k0 + (int)blockIdx.y * ppb;  // the block's pods: [kb, kb + ppb)
+  const int lim = min(N, n_hi);
+  const bool lds = lkeys > 0 && job.c.n_keys <= lkeys;
+  if (lds) {  // every lane reaches the barrier (no early exit above it)
+    const int nk = job.c.n_keys;
+    for (int i = (int)threadIdx.x; i < nk * 1024; i += 256) {
+      const int key = i >> 10, j = i & 1023;
+      slab[i] = nb + j < lim ? gp(job.c.label_value)[(size_t)key * N + nb + j] : -1;
+    }
+    __syncthreads();
+  }
+  if (kb >= kend || n >= lim) return;
+  const int cnt = min(4, lim - n);
+  uint32_t* stat = job.stat;
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(stat);
+  const bool quad = cnt == 4 && ((N | n_lo) & 3) == 0 && (sa & 15) == 0;
+  const bool pair = ((N | n_lo) & 1) == 0 && (sa & 7) == 0;  // 8-byte pairs at even offsets
+  const DevCluster c = job.c;
+  const DevPodsK P = pods_k(job.P);
+  const kss_profile prof = DEF ? default_profile_c() : prof_arg;
+  uint32_t f[4];
+  uint64_t th[4], ts[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int ni = n + min(i, cnt - 1);
+    f[i] = gp(c.node_flags)[ni];
+    th[i] = gp(c.taint_hard)[ni];
+    ts[i] = gp(c.taint_soft)[ni];
+  }
+  for (int t = 0; t < ppb; t++) {
+    const int k = kb + t;
+    if (k >= kend) break;
+    const auto& pod = P.pods[k];
+    uint32_t w[4];
+    if (lds)
+      static_words4(c, P, pod, prof, n, cnt, f, th, ts,
+                    [&](int key, int i) { return slab[(key << 10) + (n + min(i, cnt - 1) - nb)]; }, w);
+    else
+      static_words4(c, P, pod, prof, n, cnt, f, th, ts,
+                    [&](int key, int i) {
+                      const int ni = n + min(i, cnt - 1);
+                      return c.ncl ? label_of(c, key, ni) : gp(c.label_value)[(size_t)key * N + ni];
+                    }, w);
+    {  // the ImageLocality score above the narrowed NodeAffinity field
+      int64_t sum[4] = {0, 0, 0, 0};
+      const int il_n = pod.img_len;
+      for (int j = 0; j < il_n; j++) {
+        const size_t row = (size_t)P.ints[pod.img_off + j] * (size_t)N;
+#pragma unroll
+        for (int i = 0; i < 4; i++) sum[i] += gp(c.image_score)[row + (size_t)(n + min(i, cnt - 1))];
+      }
+      const int nc = pod.n_containers;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const uint32_t il = il_n > 0 && (w[i] & 7u) == 0 ? (uint32_t)image_priority(sum[i], nc) : 0u;
+        w[i] = (w[i] & ((1u << SWPI_IL_SHIFT) - 1u)) | (il << SWPI_IL_SHIFT);
+      }
+    }
     uint32_t* dst = &stat[(size_t)(row0 + k - k0) * N + n];  // row0: the half of a double-buffered table
     if (quad) {
       st_ag16(dst, kss_u32x4{w[0], w[1], w[2], w[3]});
@@ -806,6 +935,11 @@ struct kss_ctx {
   DevBuf spod_buf, stat_buf;
   std::vector<SPod> spod_host;
   bool spod_ok = false;
+  // the ports-and-images form (option simple_ports_images): the staged batch holds a NodePorts /
+  // ImageLocality pod and k_simple_pi takes it; the pods' port masks beside their records
+  bool spod_pi = false;
+  DevBuf sport_buf;
+  std::vector<SPort> sport_host;
   bool staged_names = false;  // some staged pod has a NodeAffinity PreFilterResult node list
   // host-resolved programs of the staged pods for k_spread (gpod_ok false: k_schedule)
   DevBuf gpod_buf;
@@ -1135,13 +1269,17 @@ bool f64_exact(const F64Bounds& c, const F64Bounds& p, int n_pods) {
          c.max_nz0 + (double)n_pods * p.max_cnz < lim;
 }
 
+// A pod of the ports-and-images form (k_simple_pi): host ports or node-cached images.
+bool pod_ports_images(const kss_pod& p) { return (p.port_conflict | p.port_add) != 0 || p.img_len > 0; }
+
 // Compact record of one pod (kss_simple.cuh SPod); false when the preferred NodeAffinity
-// weights do not fit the static word's 20 bits.
-bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q) {
-  if (p.port_conflict | p.port_add || p.img_len > 0 || p.vol_len > 0) return false;  // NodePorts / ImageLocality / volumes: k_schedule
+// weights do not fit the static word's 20 bits.  pi: a record of the ports-and-images form, which
+// admits NodePorts / ImageLocality pods and whose static word holds 13 bits of NodeAffinity.
+bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, bool pi = false) {
+  if ((!pi && pod_ports_images(p)) || p.vol_len > 0) return false;  // NodePorts / ImageLocality / volumes: k_schedule
   int64_t wsum = 0;
   for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
-  if (wsum > 0xFFFFF) return false;  // static word: 20 bits of raw NodeAffinity
+  if (wsum > (pi ? (int64_t)SWPI_NA_MAX : 0xFFFFF)) return false;  // static word: 20 (13) bits of raw NodeAffinity
   q = SPod{};
   bool all_zero = true;
   for (int r = 0; r < 3 + n_scalar; r++) all_zero &= p.fit_request[r] == 0;
@@ -1168,13 +1306,40 @@ bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q) {
 // Compact records of every pod of a (validated) podset for k_simple; false when some pod
 // needs another kernel (spread / inter-pod-affinity programs, or fill_spod refuses it).
 // n_shapes (optional): the batch's resource shapes (SPod::shape, SPod::shape_rep).
-bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr) {
+// pi (optional; the callers that route a batch to k_simple_pi): with the option
+// simple_ports_images on, a batch that holds a NodePorts / ImageLocality pod gets records of the
+// ports-and-images form (pi->form; pi->ports: the pods' masks); pi->na_pod: the pod whose
+// preferred NodeAffinity weights exceed that form's 13 bits (-1 none).  A batch without such a pod
+// is built exactly as without pi.
+struct PiRecords {
+  bool form = false;
+  int na_pod = -1;
+  std::vector<SPort> ports;
+};
+bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr,
+                 PiRecords* pi = nullptr) {
   out.assign((size_t)std::max(ps->n_pods, 1), SPod{});
   if (n_shapes) *n_shapes = 0;
+  bool form = false;
+  if (pi) {
+    *pi = PiRecords{};
+    if (opt(O_SIMPLE_PI))
+      for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
+    pi->form = form;
+    if (form) pi->ports.assign((size_t)std::max(ps->n_pods, 1), SPort{});
+  }
   for (int i = 0; i < ps->n_pods; i++) {
     const kss_pod& p = ps->pods[i];
     if (p.n_hard | p.n_soft | p.ipa_len) return false;
-    if (!fill_spod(ps, p, n_scalar, out[(size_t)i])) return false;
+    if (!fill_spod(ps, p, n_scalar, out[(size_t)i], form)) {
+      if (form && p.vol_len == 0) {  // the form's own limit: weights the 20-bit field would hold
+        int64_t wsum = 0;
+        for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
+        if (wsum <= 0xFFFFF) pi->na_pod = i;
+      }
+      return false;
+    }
+    if (form) pi->ports[(size_t)i] = SPort{p.port_conflict, p.port_add};
   }
   const int n = ps->n_pods;
   std::vector<kss_shape_key> keys((size_t)n);
@@ -1215,6 +1380,7 @@ enum {
   GP_PORTS_IMAGES,
   GP_PCT,
   GP_SCALAR_SCORED,
+  GP_PI_NA_WEIGHTS,
   GP_NCODES
 };
 const char* const kGpReason[GP_NCODES] = {
@@ -1235,6 +1401,8 @@ const char* const kGpReason[GP_NCODES] = {
     "percentageOfNodesToScore below 100 (numFeasibleNodesToFind / nextStartNodeIndex window): k_simple, and k_spread "
     "under the default profile, for pods without a NodeAffinity PreFilterResult list, else k_schedule",
     "the profile scores an extended (scalar) resource and the cluster has extended resources: k_schedule only",
+    "preferred NodeAffinity weights above 8191 in a batch with host ports or node-cached images (k_simple's "
+    "ports-and-images form keeps 13 bits of raw NodeAffinity): k_schedule only",
 };
 
 bool gfail(GpodNeeds& need, int code, int pod) {
@@ -1856,6 +2024,7 @@ void kss_destroy(kss_ctx* ctx) {
   ctx->chosen_buf.release();
   ctx->job_buf.release();
   ctx->spod_buf.release();
+  ctx->sport_buf.release();
   ctx->stat_buf.release();
   ctx->bound_buf.release();
   ctx->pre_buf.release();
@@ -2734,10 +2903,10 @@ static bool same_profile(const kss_profile& a, const kss_profile& b) {
 // re-evaluates the candidate after the previous commit).
 static int simple_cap(const Geometry& g) { return g.npt * g.threads; }
 
-static bool simple_fits(const Geometry& g, int nsc) {
+static bool simple_fits(const Geometry& g, int nsc, bool pi = false) {  // pi: k_simple_pi's LDS
   const int pf_n = g.threads > 64 ? g.threads - 64 : g.threads;  // prefetch lanes (kss_simple.cuh)
   return g.W <= 64 * SX_CHUNKS && g.npt <= KSS_MAX_NPT && (simple_cap(g) + pf_n - 1) / pf_n <= PF_MAX &&
-         simple_lds_bytes(simple_cap(g), nsc) <= KSS_LDS_BUDGET;
+         (pi ? simple_lds_bytes_pi(simple_cap(g), nsc) : simple_lds_bytes(simple_cap(g), nsc)) <= KSS_LDS_BUDGET;
 }
 
 // k_simple's shape table (k_simple_tab) for a batch of n_shapes resource shapes on geometry g:
@@ -2841,7 +3010,7 @@ static void static_rows(const Geometry& g, const XPeers& X, int max_nodes, int& 
 // k_static over pods [k0, k1) x rows [n_lo, n_hi) of n_jobs jobs; max_keys: the jobs' largest label-key count
 // (the LDS label copy when it is at most STATIC_LKEYS)
 static void launch_static(hipStream_t st, bool def, const DevJob* jobs, const kss_profile& pr, int n_jobs, int k0, int k1,
-                          int n_lo, int n_hi, int max_keys, int row0 = 0) {
+                          int n_lo, int n_hi, int max_keys, int row0 = 0, bool pi = false) {
   const int lk = max_keys > 0 && max_keys <= STATIC_LKEYS ? max_keys : 0;
   // pods per block: with the LDS label copy, enough pods to amortise loading it (C5: 64 pods of
   // 1,000 nodes per block; r6c: 8 / 16 / 32 / 64 within 1 % of each other)
@@ -2850,7 +3019,11 @@ static void launch_static(hipStream_t st, bool def, const DevJob* jobs, const ks
   const dim3 sgrid((unsigned)(std::max(n_hi - n_lo, 1) + 1023) / 1024, (unsigned)((k1 - k0 + ppb - 1) / ppb),
                    (unsigned)n_jobs);
   const size_t sh = sizeof(int32_t) * 1024 * (size_t)lk;
-  if (def)
+  if (pi && def)  // the ports-and-images form of the word (k_simple_pi reads it)
+    hipLaunchKernelGGL(k_static_pi<true>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
+  else if (pi)
+    hipLaunchKernelGGL(k_static_pi<false>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
+  else if (def)
     hipLaunchKernelGGL(k_static<true>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
   else
     hipLaunchKernelGGL(k_static<false>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
@@ -2863,7 +3036,8 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          unsigned long long* stamps = nullptr, hipEvent_t* ev = nullptr, const SplitRun* split = nullptr,
                          int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
                          hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
-                         int n_shapes = 0, bool flat = false) {
+                         int n_shapes = 0, bool flat = false, const SPort* sports = nullptr) {
+  const bool pi = sports != nullptr;  // the ports-and-images form (one job): k_static_pi + k_simple_pi
   // st2 (with pev, two events per chunk): the static words of chunk i+1 are computed on st2 into the
   // other half of a double-buffered table while k_simple runs chunk i on st (each job's table holds
   // 2 x chunk rows); k_simple of chunk i waits for its k_static, k_static of chunk i+1 for
@@ -2874,8 +3048,9 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   // launch with the same nextStartNodeIndex in its own cursor word, simple_schedule)
   const bool win = k_find > 0;
   // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
-  const bool tab = n_shapes > 0 && def && !win && nsc == 0;
-  const size_t shmem = simple_lds_bytes(cap, nsc, tab ? n_shapes : 0);
+  // (pi: no shape table)
+  const bool tab = n_shapes > 0 && def && !win && nsc == 0 && !pi;
+  const size_t shmem = pi ? simple_lds_bytes_pi(cap, nsc) : simple_lds_bytes(cap, nsc, tab ? n_shapes : 0);
   // flat: the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
   flat = flat && tab && n_jobs == 1 && !(split && split->X.n > 1);
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
@@ -2883,6 +3058,8 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
   const void* fn = flat  ? (const void*)k_simple_tab_flat
                    : tab ? (const void*)k_simple_tab
+                   : pi  ? (win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
+                                : (def ? (const void*)k_simple_pi<true, false> : (const void*)k_simple_pi<false, false>))
                    : win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
                          : (def ? (const void*)k_simple<true, false> : (const void*)k_simple<false, false>);
   int last_arg = tab ? n_shapes : k_find;  // k_simple_tab: n_shapes in k_find's place
@@ -2906,7 +3083,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     // (*pev)[2i]: k_static of chunk i done (st2), (*pev)[2i+1]: k_simple of chunk i done (st)
     HIP_TRY(hipEventRecord((*pev)[1], st));  // st's work so far (the reset) before st2 writes the table
     HIP_TRY(hipStreamWaitEvent(st2, (*pev)[1], 0));
-    launch_static(st2, def, jobs, pr, n_jobs, 0, std::min(n_pods_max, chunk), n_lo, n_hi, max_keys, 0);
+    launch_static(st2, def, jobs, pr, n_jobs, 0, std::min(n_pods_max, chunk), n_lo, n_hi, max_keys, 0, pi);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord((*pev)[0], st2));
   }
@@ -2919,12 +3096,12 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
       if (k1 < n_pods_max) {  // the next chunk's, into the other half, once chunk ci-1 no longer reads it
         if (ci_ > 0) HIP_TRY(hipStreamWaitEvent(st2, (*pev)[2 * (ci_ - 1) + 1], 0));
         launch_static(st2, def, jobs, pr, n_jobs, k1, std::min(n_pods_max, k1 + chunk), n_lo, n_hi, max_keys,
-                      ((ci_ + 1) & 1) * chunk);
+                      ((ci_ + 1) & 1) * chunk, pi);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord((*pev)[2 * (ci_ + 1)], st2));
       }
     } else {
-      launch_static(st, def, jobs, pr, n_jobs, k0, k1, n_lo, n_hi, max_keys);
+      launch_static(st, def, jobs, pr, n_jobs, k0, k1, n_lo, n_hi, max_keys, 0, pi);
       HIP_TRY(hipGetLastError());
     }
     unsigned epoch0 = 0;
@@ -2937,7 +3114,8 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     }
     unsigned long long* sp = k0 == 0 ? stamps : nullptr;
     void* args[] = {(void*)&jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
-                    (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg};
+                    (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg,
+                    (void*)&sports};  // (k_simple_pi's trailing argument; the other kernels take 13)
     const int ci = k0 / chunk;
     if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
     if (xcd) {
@@ -3205,7 +3383,9 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (nomq && split) return fail(KSS_E_UNSUPPORTED, "split grids do not read the nominator");
   const bool simple_ok = simple_win_ok && !nomq && staged && ctx->spod_ok && commit && !record && !keep_norm && !need.general &&
                          scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
-                         !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL);
+                         !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
+                         // the ports-and-images form: one part, and the option still on (it is process-wide)
+                         (!ctx->spod_pi || (!split && opt(O_SIMPLE_PI)));
   if (simple_ok && ctx->force_w <= 0 && !split) W = std::min(W, 64 * SX_CHUNKS);
   // XCD-local k_simple (launch_simple xcd, xcd_slot): a cluster whose shards fit one XCD's CUs
   // at one node per lane runs every shard on XCD 0, so the per-pod exchange stays in that
@@ -3246,7 +3426,8 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (split && ctx->split_wl > ctx->n_cu) return fail(KSS_E_UNSUPPORTED, "split grid: more shards per part than CUs");
   Geometry g;
   if (!pick_geometry((int)N, W, ctx->pref_threads, g)) return fail(KSS_E_UNSUPPORTED, "no geometry for this cluster");
-  const bool simple = simple_ok && simple_fits(g, ctx->dc.n_scalar);
+  const bool simple = simple_ok && simple_fits(g, ctx->dc.n_scalar, ctx->spod_pi);
+  const bool simple_pi = simple && ctx->spod_pi;
   const int n_res = (int)ctx->gneed.res_rows.size();
   bool spread = spread_ok && spread_fits(g, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar);
   if (spread && !simple && opt(O_THREADS) <= 0 && opt(O_FORCE_THREADS) <= 0) {
@@ -3447,7 +3628,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   ctx->last_xcd[0] = (simple && xcd_try && g.W > 1) || xcd_spread ? 1 : 0;
   ctx->last_xcd[1] = 0;
   // the shape table: the whole staged batch (its shape directory sits in its first records)
-  const bool tab = simple && opt(O_SHAPE_TABLE) && n == ctx->staged_n &&
+  const bool tab = simple && !simple_pi && opt(O_SHAPE_TABLE) && n == ctx->staged_n &&
                    shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
   ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;
   ctx->last_shape[1] = tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
@@ -3457,7 +3638,8 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (simple)
     rc = launch_simple(ctx->stream, g, 1, jd, ctx->prof, n, (int)N, chunk, gran, gb,
                        errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr, ctx->dc.n_scalar, ctx->last_xcd[0] != 0,
-                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0, flat);
+                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0, flat,
+                       simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr);
   else if (spread)
   {
     const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar);
@@ -3582,7 +3764,10 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
     ctx->staged_max_own = std::max(ctx->staged_max_own, (int)ps->pods[i].own_terms_len);
     ctx->staged_names |= ps->pods[i].names_len >= 0;
   }
-  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes);
+  PiRecords pi;
+  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi);
+  ctx->spod_pi = ctx->spod_ok && pi.form;
+  ctx->sport_host.swap(pi.ports);
   ctx->gpod_ok = false;
   if (!ctx->spod_ok) {  // programs: the resolved records of k_spread
     ctx->gpod_ok = build_gpods(ps, ctx->dc.n_scalar, ctx->dc.n_classes, ctx->key_card_h.data(), ctx->key_flags_h.data(),
@@ -3602,6 +3787,11 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ctx->spod_buf.p, ctx->spod_host.data(), sizeof(SPod) * ctx->spod_host.size(),
                          hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->spod_pi) {
+    if ((rc = ctx->sport_buf.ensure(sizeof(SPort) * ctx->sport_host.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->sport_buf.p, ctx->sport_host.data(), sizeof(SPort) * ctx->sport_host.size(),
+                           hipMemcpyHostToDevice, ctx->stream));
+  }
   return 0;
 }
 
@@ -4169,7 +4359,7 @@ static int svc_start_locked(kss_ctx* ctx) {
   // no extended resources, exact f64 arithmetic, W <= 64 (its exchange:
   // one lane per shard), the node rows cached in LDS (checked below); KSS_SERVICE_GENERAL=1 keeps
   // the general chain, for comparison.  On an XCD-local grid when its shards fit one XCD's CUs.
-  const bool simple_pre = ctx->spod_ok && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
+  const bool simple_pre = ctx->spod_ok && !ctx->spod_pi && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
                           f64_exact(ctx->f64_cluster, ctx->f64_pods, ctx->staged_n) && !opt(O_SERVICE_GENERAL);
   const int xcd_cus = ctx->n_cu / XCD_GRID_MULT;
   // (off by default: the record's stores to host memory from one XCD were slower than the L2
@@ -5359,7 +5549,8 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   out3[0] = 0;
   out3[1] = -1;
   out3[2] = GP_OK;
-  if (build_spods(ps, cl->n_scalar, sp)) {
+  PiRecords pi;  // (follows the process-wide option simple_ports_images)
+  if (build_spods(ps, cl->n_scalar, sp, nullptr, &pi)) {
     out3[0] = 1;
     return 0;
   }
@@ -5371,6 +5562,10 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   }
   out3[1] = need.fail_pod;
   out3[2] = need.fail_code;
+  if (pi.form && pi.na_pod >= 0 && need.fail_code == GP_PORTS_IMAGES) {  // the form's own limit kept it off k_simple
+    out3[1] = pi.na_pod;
+    out3[2] = GP_PI_NA_WEIGHTS;
+  }
   return 0;
 }
 

@@ -238,6 +238,19 @@ __device__ __forceinline__ int sw_code(uint32_t w) {
 __device__ __forceinline__ int sw_tt(uint32_t w) { return (int)((w >> 5) & 0x7Fu); }
 __device__ __forceinline__ int sw_na(uint32_t w) { return (int)(w >> 12); }
 
+// The ports-and-images form (PI: k_static_pi, k_simple_pi) of the static word: raw
+// NodeAffinity narrows to 13 bits (bits 12-24; host-checked: every pod's Σ positive preferred
+// weights <= SWPI_NA_MAX) and bits 25-31 hold the ImageLocality score (0..100; final, it has no
+// NormalizeScore); both 0 unless bits 0-2 are 0.  The other fields are where they were.
+constexpr uint32_t SWPI_NA_BITS = 13, SWPI_NA_MAX = (1u << SWPI_NA_BITS) - 1u, SWPI_IL_SHIFT = 12 + SWPI_NA_BITS;
+// A pod's NodePorts masks over the cluster's port dictionary (kss_pod.port_conflict / port_add),
+// beside its SPod in the PI form: a parallel array in HBM and a ring of its own in LDS, so SPod
+// does not grow.
+struct alignas(16) SPort {
+  uint64_t conflict, add;
+};
+static_assert(sizeof(SPort) == 16, "SPort is copied as uint4");
+
 // lab(key): the node's interned label value (label_of by default; k_static reads an LDS copy)
 template <class Lab>
 __device__ __forceinline__ uint32_t static_word_l(const DevCluster& c, const DevPods& P, const kss_pod& p,
@@ -561,6 +574,17 @@ __device__ __forceinline__ long long simple_key(const kss_profile& prof, const S
     if ((se >> KSS_S_BALANCED_ALLOCATION) & 1u) total += (int64_t)e.ba * prof.weight[KSS_S_BALANCED_ALLOCATION];
   }
   return (long long)(((unsigned long long)(uint32_t)total << 32) | (0xFFFFFFFFull - g));
+}
+
+// PI form, pass B: e.fit as pass A left it in its cv column (pi_fix) -> the Fit score back in
+// e.fit; returns what ImageLocality adds to the selectHost key: its raw score is its final score
+// (no NormalizeScore), times its weight, in the key's total field.
+template <bool DEF>
+__device__ __forceinline__ long long pi_key_add(const kss_profile& prof, SVal& e, bool scored) {
+  const int il = e.fit >> 8;
+  e.fit &= 0xFF;
+  const bool on = scored && (DEF || ((prof.score_enabled >> KSS_S_IMAGE_LOCALITY) & 1u));
+  return on ? (long long)((unsigned long long)(uint32_t)(il * prof.weight[KSS_S_IMAGE_LOCALITY]) << 32) : 0ll;
 }
 
 // ---------------------------------------------------------------------------
@@ -916,6 +940,12 @@ __host__ __device__ inline size_t simple_lds_bytes(int cap, int nsc = 0, int n_s
   return n_shapes > 0 ? (base + 15) / 16 * 16 + shape_tab_bytes(cap, n_shapes) : base;
 }
 
+// The PI form's LDS behind the shard's (no shape table in this form): the ring of the pods' port
+// masks (ring slot = pod % RING, as the record ring) and the UsedPorts column, one word per slot.
+__host__ __device__ inline size_t simple_lds_bytes_pi(int cap, int nsc) {
+  return (simple_lds_bytes(cap, nsc) + 15) / 16 * 16 + RING * sizeof(SPort) + 8 * (size_t)cap;
+}
+
 struct ShapeTab {
   uint64_t* shp;   // [SSHAPE_WORDS][n_shapes]: the shapes' SShape records, staged once per launch, word by word
                    // (lane = shape reads consecutive words: no bank conflict)
@@ -1057,15 +1087,31 @@ __device__ __forceinline__ SVal dyn_eval_def(const Q& q, uint32_t w, const DynRo
   return e;
 }
 
+// PI form, after an evaluation on a PI static word (whose e.na still carries the ImageLocality
+// score above the 13 NodeAffinity bits): the NodePorts verdict (used: the node's UsedPorts bits,
+// with the previous pod's port_add in the H1 evaluation; a node failing NodeResourcesFit keeps
+// that verdict -- an unrecorded batch shows only that the node is infeasible), the NodeAffinity
+// field, and the ImageLocality score moved above the Fit score (<= 100), the cv column in which it
+// reaches pass B.
+template <bool DEF>
+__device__ __forceinline__ void pi_fix(const kss_profile& prof, SVal& e, uint64_t used, uint64_t conflict) {
+  const bool en = DEF || ((prof.filter_enabled >> KSS_F_NODE_PORTS) & 1u);
+  e.f = (e.f == 0 && en && (used & conflict) != 0) ? KSS_F_NODE_PORTS : e.f;
+  const int il = e.na >> SWPI_NA_BITS;
+  e.na &= (int)SWPI_NA_MAX;
+  e.fit |= il << 8;
+}
+
 // Pass A for pod q (static words in ring slot `sl`) over the shard's `own` nodes on the
 // current state (H0), plus the candidate slot `cand_s` (-1 none) re-evaluated with the
 // previous pod `q0` committed on it (H1), by the first slot without a node (slot `own`,
 // which is slot `cap` of lane 0 when the shard is full).  st = {nf0, tt0, na0, nf1, tt1, na1}.
 // Both records are copied to registers before the node loop (its LDS stores would otherwise
 // make the compiler re-read every record field inside the loop, one LDS round trip each).
-template <bool DEF>
+template <bool DEF, bool PI = false>
 __device__ __forceinline__ void simple_pass_a(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
-                                              const SimpleShard& L, int sl, int own, int cand_s, long long (&st)[6]) {
+                                              const SimpleShard& L, int sl, int own, int cand_s, long long (&st)[6],
+                                              const uint64_t* pused = nullptr, SPort qp = SPort{}, uint64_t q0add = 0) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1085,6 +1131,7 @@ __device__ __forceinline__ void simple_pass_a(const kss_profile& prof, const SPo
     DynRow r = shard_row(L, ns);
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
+    if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap : s, e);
     // H0 counts the shard's own slots, H1 every slot but the candidate's (whose H1 value is
@@ -1111,10 +1158,11 @@ __device__ __forceinline__ void simple_pass_a(const kss_profile& prof, const SPo
 // reduces its best key by itself: the waves' bests ride with the statistics, one workgroup
 // reduction per pod instead of two (simple_sync_pw).  u = the wave lane's {nf0, tt0, na0, nf1,
 // tt1, na1} (H1: the wave's slots but its candidate, plus the candidate re-evaluated).
-template <bool DEF>
+template <bool DEF, bool PI = false>
 __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                                  const SimpleShard& L, int sl, int own, int pwv, int cand_w,
-                                                 uint32_t (&u)[6]) {
+                                                 uint32_t (&u)[6], const uint64_t* pused = nullptr, SPort qp = SPort{},
+                                                 uint64_t q0add = 0) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1136,6 +1184,7 @@ __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const 
     DynRow r = shard_row(L, ns);
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
+    if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap + wv : s, e);
     const bool c0 = e.f == 0 && !extra, c1 = e.f == 0 && (extra || s != cand_w);
@@ -1155,8 +1204,13 @@ __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const 
 // following each other on one lane (r7c A/B against one lane adding every row: C2 284.7k ->
 // 290.7k pods/s, C4 unchanged; the one-lane form is retired, DESIGN.md "Retired A/B switches").
 static_assert(offsetof(SPod, cnz) == offsetof(SPod, creq) + 3 * sizeof(double), "creq, cnz adjacent");
-__device__ __forceinline__ void simple_commit_lanes(const SimpleShard& L, const SPod& pk, int s, int lane) {
+template <bool PI = false>
+__device__ __forceinline__ void simple_commit_lanes(const SimpleShard& L, const SPod& pk, int s, int lane,
+                                                    uint64_t* pused = nullptr, uint64_t padd = 0) {
   const int cap = L.cap;
+  if constexpr (PI) {  // NodeInfo.UsedPorts: the pod's host ports
+    if (lane == 6) pused[s] |= padd;
+  }
   if (lane < 5) L.r64[(3 + lane) * cap + s] += (&pk.creq[0])[lane];
   if (lane == 5) L.r32[s] += 1;
   if (lane >= 8 && lane < 8 + L.nsc) L.sc[(size_t)(L.nsc + lane - 8) * cap + s] += pk.sc_req[lane - 8];
@@ -1173,12 +1227,13 @@ __device__ __forceinline__ void simple_commit_lanes(const SimpleShard& L, const 
 // wave polling for itself, with no closing barrier, lost (r8t A/B: C2 261k against 304k pods/s):
 // the prefetch waves' polls queue behind their own HBM prefetch loads (vmcnt is in order), so
 // the pod waits for them.  (Retired: DESIGN.md "Retired A/B switches".)
-template <typename Idle>
+template <bool PI = false, typename Idle>
 __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long long wbest, uint32_t (&u)[6], int W,
                                                int w, unsigned epoch, unsigned long long* gran, const XPeers& X,
                                                int* err, int per, int node_base, int lo, int own, const SPod& pk,
                                                bool commit, const SimpleShard& L, int kb, long long (&R)[4],
-                                               KSS_GLOBAL unsigned long long* sp, Idle&& idle) {
+                                               KSS_GLOBAL unsigned long long* sp, Idle&& idle,
+                                               uint64_t* pused = nullptr, uint64_t padd = 0) {
   wave_red_stats_pw(u);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   if (sp && threadIdx.x == 0) sp[7] = wall_clock64();
@@ -1228,13 +1283,13 @@ __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long l
         H.res[2] = h1 ? t[4] : t[1];
         H.res[3] = h1 ? t[5] : t[2];
       }
-      if (commit && h1) simple_commit_lanes(L, pk, slot, lane);
+      if (commit && h1) simple_commit_lanes<PI>(L, pk, slot, lane, pused, padd);
     } else {
       const long long v[7] = {best, t[0], t[1], t[2], t[3], t[4], t[5]};
       if (simple_exchange(H, gran, X, W, w, epoch, err, v, per, node_base, kb) && commit) {
         const long long K = H.res[0];  // (written by lane 0 of this wave: in order)
         const int x = key_node(K, node_base, lo);
-        if (x >= 0 && x < own) simple_commit_lanes(L, pk, x, lane);
+        if (x >= 0 && x < own) simple_commit_lanes<PI>(L, pk, x, lane, pused, padd);
       }
     }
   }
@@ -1286,10 +1341,11 @@ __device__ __forceinline__ void win_acc(uint32_t (&u)[12], bool c0, bool c1, int
 }
 
 // simple_pass_a with the window's split: part a / b of each slot by its node against `start`
-template <bool DEF>
+template <bool DEF, bool PI = false>
 __device__ __forceinline__ void simple_pass_a_win(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                                   const SimpleShard& L, int sl, int own, int cand_s, int lo, int start,
-                                                  uint32_t (&u)[12]) {
+                                                  uint32_t (&u)[12], const uint64_t* pused = nullptr, SPort qp = SPort{},
+                                                  uint64_t q0add = 0) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1309,6 +1365,7 @@ __device__ __forceinline__ void simple_pass_a_win(const kss_profile& prof, const
     DynRow r = shard_row(L, ns);
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
+    if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap : s, e);
     win_acc(u, e.f == 0 && !extra, e.f == 0 && s != cand_s, lo + ns >= start ? 0 : 1, e);
@@ -1316,10 +1373,11 @@ __device__ __forceinline__ void simple_pass_a_win(const kss_profile& prof, const
 }
 
 // simple_pass_a_pw with the window's split
-template <bool DEF>
+template <bool DEF, bool PI = false>
 __device__ __forceinline__ void simple_pass_a_pw_win(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                                      const SimpleShard& L, int sl, int own, int pwv, int cand_w, int lo,
-                                                     int start, uint32_t (&u)[12]) {
+                                                     int start, uint32_t (&u)[12], const uint64_t* pused = nullptr,
+                                                     SPort qp = SPort{}, uint64_t q0add = 0) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1340,6 +1398,7 @@ __device__ __forceinline__ void simple_pass_a_pw_win(const kss_profile& prof, co
     DynRow r = shard_row(L, ns);
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
+    if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap + wv : s, e);
     win_acc(u, e.f == 0 && !extra, e.f == 0 && (extra || s != cand_w), lo + ns >= start ? 0 : 1, e);
@@ -1461,13 +1520,14 @@ __device__ __forceinline__ void win_cut_scan(SimpleHdr& H, const SimpleShard& L,
 // k+1's cut segment (part * W + shard, -1: no cut), d_out = its dropped node (on the cut shard;
 // -1 elsewhere).  start: this shard's split of pod k+1's node list (win_start).  False if the
 // launch aborted.
-template <bool PW, typename Idle>
+template <bool PW, bool PI = false, typename Idle>
 __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long long wkey, uint32_t (&u)[12], int W,
                                                 int w, unsigned epoch, unsigned long long* gran, const XPeers& X,
                                                 int* err, int per, int node_base, int lo, int own, const SPod& pk,
                                                 bool commit, const SimpleShard& L, int kb, int k_find, int start,
                                                 int pwv, long long (&R)[4], int& d_out, int& cs_out,
-                                                KSS_GLOBAL unsigned long long* sp, Idle&& idle) {
+                                                KSS_GLOBAL unsigned long long* sp, Idle&& idle,
+                                                uint64_t* pused = nullptr, uint64_t padd = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   if (PW) {
     // one node (or the H1 re-evaluation) per lane: the four counts are ballot popcounts, the four
@@ -1718,7 +1778,7 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
       // reads that row without a barrier of its own)
       if (commit && gbest != 0) {
         const int x = gl - lo;
-        if (x >= 0 && x < own) simple_commit_lanes(L, pk, x, lane);
+        if (x >= 0 && x < own) simple_commit_lanes<PI>(L, pk, x, lane, pused, padd);
       }
       if (lane == 0) {
         H.res[0] = gbest;
@@ -1808,16 +1868,27 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
 // < 100 (simple_sync_win): k_find = numFeasibleNodesToFind, cursor = the cluster's nextStartNodeIndex
 // word (read at the start; written back at the end by the start shard, on a split grid by the first
 // shard of every part from the start shard's granule).
-template <bool DEF, bool PW, bool WIN>
+// PI: the ports-and-images form (k_simple_pi).  The static words are k_static_pi's; sports
+// holds the pods' NodePorts masks.  The UsedPorts column `pused` is node state like the rows: loaded
+// with them, written back with them (so a chunked batch carries it from launch to launch through
+// the same hand-off), committed with the row (simple_commit_lanes: same wave, same place relative
+// to the barriers), read by pass A next to the row -- H1 with pod k's port_add ORed in, as H1 adds
+// pod k's requests to the row.  The masks' ring is stored where the record ring is.
+template <bool DEF, bool PW, bool WIN, bool PI = false>
 __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __restrict__ spods,
                                                 const uint32_t* __restrict__ stat, const int32_t* __restrict__ ints,
                                                 int k0, int k1, int32_t* chosen, PodMeta* meta, const kss_profile& prof,
                                                 int W, int w, int cap, unsigned long long* gran, const XPeers& X,
                                                 unsigned epoch0, int* err, unsigned long long* stamps, long long* smem,
-                                                int k_find = 0, int32_t* cursor = nullptr) {
+                                                int k_find = 0, int32_t* cursor = nullptr,
+                                                const SPort* __restrict__ sports = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x;
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
   const SimpleShard L = shard_view(reinterpret_cast<uint8_t*>(smem) + sizeof(SimpleHdr), cap, c.n_scalar);
+  SPort* const pring =
+      PI ? reinterpret_cast<SPort*>(reinterpret_cast<uint8_t*>(smem) + (simple_lds_bytes(cap, c.n_scalar) + 15) / 16 * 16)
+         : nullptr;
+  uint64_t* const pused = PI ? reinterpret_cast<uint64_t*>(pring + RING) : nullptr;
   const size_t N = (size_t)c.N;
   const int per = (c.N + W - 1) / W;
   const int lo = min(c.N, w * per), hi = min(c.N, lo + per), own = hi - lo;
@@ -1847,10 +1918,16 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       L.sc[(size_t)(L.nsc + i) * cap + s] = ld_ag(&c.requested[(size_t)(3 + i) * N + n]);
     }
     for (int d = 0; d < PD && k0 + d < k1; d++) L.st[((k0 + d) % RING) * cap + s] = ld_ag(&stat[(size_t)d * N + lo + s]);
+    if constexpr (PI) pused[s] = ld_ag(&c.port_used[n]);
   }
   for (int i = tid; i < min(k1 - k0, PD) * NQ; i += nt) {
     const int j = k0 + i / NQ;
     reinterpret_cast<uint4*>(L.ring + j % RING)[i % NQ] = reinterpret_cast<const uint4*>(spods + j)[i % NQ];
+  }
+  if constexpr (PI) {
+    for (int i = tid; i < RING; i += nt) pring[i] = SPort{};  // (the prologue iteration reads the slot of pod k0 - 1)
+    __syncthreads();
+    for (int i = tid; i < min(k1 - k0, PD); i += nt) pring[(k0 + i) % RING] = sports[k0 + i];
   }
   if (tid == 0) H.abort = 0;
   __syncthreads();
@@ -1867,6 +1944,8 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
   KSS_GLOBAL const uint32_t* gstat = gp(stat);
   KSS_GLOBAL const uint4* gspod = gp(reinterpret_cast<const uint4*>(spods));
   KSS_GLOBAL unsigned long long* gstamps = gp(stamps);
+  KSS_GLOBAL const uint4* gsport = gp(reinterpret_cast<const uint4*>(sports));
+  uint4 pfp = make_uint4(0, 0, 0, 0);  // PI: the prefetched port masks of pod k+PD
   long long st[6], R[4] = {0, 0, 0, 0};
   // the outcome of pod pend_k, not yet stored (thread out_tid of shard w_off)
   const int out_tid = (nt >> 6) > 1 ? 64 : 0;
@@ -1926,6 +2005,10 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       if (pf_on) {
         KSS_GLOBAL const uint4& src = gspod[(size_t)(k + PD) * NQ + min(pf_lane, NQ - 1)];
         pfq = make_uint4(src.x, src.y, src.z, src.w);
+        if constexpr (PI) {  // (every prefetch lane the same 16 bytes)
+          KSS_GLOBAL const uint4& ps = gsport[(size_t)(k + PD)];
+          pfp = make_uint4(ps.x, ps.y, ps.z, ps.w);
+        }
 #pragma unroll
         for (int j = 0; j < PF_MAX; j++)
           if (j < pf_per) pfw[j] = ld_ag(&gstat[(size_t)(k + PD - k0) * N + lo + min(j * pf_n + pf_lane, own - 1)]);
@@ -1934,6 +2017,9 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     auto ring_store = [&]() {  // lanes past the end rewrite the last element with its own value
       if (pf_on) {
         reinterpret_cast<uint4*>(L.ring + (k + PD) % RING)[min(pf_lane, NQ - 1)] = pfq;
+        if constexpr (PI) {
+          if (pf_lane == 0) *reinterpret_cast<uint4*>(pring + (k + PD) % RING) = pfp;
+        }
 #pragma unroll
         for (int j = 0; j < PF_MAX; j++)
           if (j < pf_per) L.st[((k + PD) % RING) * cap + min(j * pf_n + pf_lane, own - 1)] = pfw[j];
@@ -1964,8 +2050,9 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       // selected: one LDS round trip per slot, no exec-mask region; the wave's best by DPP
       const int s = wv * pwv + lane;
       if (keys && lane < pwv && s < own) {
-        const SVal e = cv_get(L, s == sub_s ? sub_h : s);
-        const long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s));
+        SVal e = cv_get(L, s == sub_s ? sub_h : s);
+        const long long ilk = PI ? pi_key_add<DEF>(prof, e, scored) : 0ll;
+        const long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s)) + ilk;
         bool kept = true;
         if (WIN && wcs >= 0) {  // the node's segment before the cut segment, or before d inside it
           const int n = lo + s, seg = (n >= wsl ? 0 : W) + w;
@@ -1980,8 +2067,10 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       if (k >= k0) {
         if (keys) {
           for (int s = tid; s < own; s += nt) {
-            const SVal e = cv_get(L, s == sub_s ? sub_h : s);
-            const long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s));
+            SVal e = cv_get(L, s == sub_s ? sub_h : s);
+            const long long ilk = PI ? pi_key_add<DEF>(prof, e, scored) : 0ll;
+            const long long key =
+                simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s)) + ilk;
             bool kept = true;
             if (WIN && wcs >= 0) {
               const int n = lo + s, seg = (n >= wsl ? 0 : W) + w;
@@ -2003,6 +2092,10 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     // pass A: pod k+1 before pod k's commit, and on the candidate after it
     const SPod& qn = L.ring[(k + 1) % RING];
     const int sln = (k + 1) % RING;
+    // PI: pod k's port_add (its commit, and H1 of pod k+1) and pod k+1's masks, wave-uniform LDS
+    // reads, here and not at the top: like qn, pod k+1's slot is behind pass B's barrier (not PW)
+    const uint64_t pk_add = PI ? pring[(k + RING) % RING].add : 0ull;
+    const SPort qnp = PI ? pring[(k + 1) % RING] : SPort{};
     if constexpr (WIN) {
       // pod k+1 starts where pod k's window stopped (its dropped node, on the cut shard), else
       // where pod k started
@@ -2013,31 +2106,31 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       }
       uint32_t u[12];
       if (k + 1 < k1) {
-        if constexpr (PW) simple_pass_a_pw_win<DEF>(prof, qn, pk, L, sln, own, pwv, cand, lo, wsl, u);
-        else simple_pass_a_win<DEF>(prof, qn, pk, L, sln, own, cand, lo, wsl, u);
+        if constexpr (PW) simple_pass_a_pw_win<DEF, PI>(prof, qn, pk, L, sln, own, pwv, cand, lo, wsl, u, pused, qnp, pk_add);
+        else simple_pass_a_win<DEF, PI>(prof, qn, pk, L, sln, own, cand, lo, wsl, u, pused, qnp, pk_add);
       } else {
 #pragma unroll
         for (int i = 0; i < 12; i++) u[i] = 0;
       }
       if (sp && tid == 0) sp[3] = wall_clock64();
-      if (!simple_sync_win<PW>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0, L,
-                               kb, k_find, wsl, pwv, R, wd, wcs, sp, prefetch_idle))
+      if (!simple_sync_win<PW, PI>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0,
+                                   L, kb, k_find, wsl, pwv, R, wd, wcs, sp, prefetch_idle, pused, pk_add))
         return;
     } else if constexpr (PW) {
       uint32_t u[6];
       if (k + 1 < k1) {
-        simple_pass_a_pw<DEF>(prof, qn, pk, L, sln, own, pwv, cand, u);
+        simple_pass_a_pw<DEF, PI>(prof, qn, pk, L, sln, own, pwv, cand, u, pused, qnp, pk_add);
       } else {
 #pragma unroll
         for (int i = 0; i < 6; i++) u[i] = 0;
       }
       if (sp && tid == 0) sp[3] = wall_clock64();
-      if (!simple_sync_pw(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0, L, kb,
-                          R, sp, prefetch_idle))
+      if (!simple_sync_pw<PI>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0, L, kb,
+                              R, sp, prefetch_idle, pused, pk_add))
         return;
     } else {
       if (k + 1 < k1) {
-        simple_pass_a<DEF>(prof, qn, pk, L, sln, own, cand, st);
+        simple_pass_a<DEF, PI>(prof, qn, pk, L, sln, own, cand, st, pused, qnp, pk_add);
       } else {
 #pragma unroll
         for (int i = 0; i < 6; i++) st[i] = 0;
@@ -2054,7 +2147,7 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       const bool won = x >= lo && x < hi;
       sub_s = won ? x - lo : -1;
       sub_h = PW ? cap + (won ? (x - lo) / max(pwv, 1) : 0) : cap;
-      if (!PW && !WIN && won && tid < 64) simple_commit_lanes(L, pk, x - lo, tid);
+      if (!PW && !WIN && won && tid < 64) simple_commit_lanes<PI>(L, pk, x - lo, tid, pused, pk_add);
       // the HBM-only class / term counts are applied after the launch (k_counts): nothing in
       // this loop reads them
     }
@@ -2123,6 +2216,7 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     st_ag(&c.nonzero[N + n], (int64_t)L.r64[7 * cap + s]);
     st_ag(&c.pod_count[n], L.r32[s]);
     for (int i = 0; i < L.nsc; i++) st_ag(&c.requested[(size_t)(3 + i) * N + n], L.sc[(size_t)(L.nsc + i) * cap + s]);
+    if constexpr (PI) st_ag(&c.port_used[n], pused[s]);
   }
   handoff_release();
 }
