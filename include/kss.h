@@ -463,7 +463,11 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * without spread / inter-pod programs and without volumes whose pods hold host ports (NodePorts) or
  * node-cached images (ImageLocality) runs on k_simple's ports-and-images form instead of
  * k_schedule, on one part, provided every pod's preferred NodeAffinity weights sum to at most 8191;
- * batches without such pods are routed as with 0; kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
+ * batches without such pods are routed as with 0; kss_plan_podset and kss_plan_shapes follow it),
+ * "table_images" (default 0; effective only with "simple_ports_images" 1: a batch of that form in
+ * which no pod holds a host port runs on the shape-table loop, kss_last_shape_table, under that
+ * loop's own conditions; a batch with a host-port pod, the window, a runtime profile, one shard with
+ * "shape_table" 1 and more than KSS_MAX_SHAPES shapes run as with 0).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -804,7 +808,11 @@ int kss_last_xcd_local(kss_ctx* ctx, int32_t* out2);
  * (kss_plan_shapes) on a per-wave geometry of two or more waves keeps the state-dependent filter
  * verdict and scores of every (shape, node) in LDS and re-evaluates only the committed node per
  * pod.  Option "shape_table": 1 (default) grids of two or more shards, 2 also a single shard (no
- * exchange hides the re-evaluation there: slower, for tests), 0 never. */
+ * exchange hides the re-evaluation there: slower, for tests), 0 never.  A batch of the
+ * ports-and-images form (option "simple_ports_images") takes the table only with the option
+ * "table_images" 1 and only when none of its pods holds a host port: ImageLocality is in the static
+ * word, UsedPorts would be loop state the table does not hold.  It is reported here like any table
+ * run (out2[0] > 0); kss_last_kernel stays 1. */
 int kss_last_shape_table(kss_ctx* ctx, int32_t* out2);
 /* The shape-table loop's cross-shard exchange in the last run: out2[0] = 1 when it ran the flat
  * form, out2[1] = its entries (shards x waves; 0 otherwise).  Flat: every wave of every shard
@@ -921,7 +929,9 @@ int kss_abi_sizes(int32_t* out, int32_t n);
  * k_simple (its ports-and-images form) when it has no spread / inter-pod program and no volume and
  * every pod's Σ positive preferred NodeAffinity weights is <= 8191 (else k_schedule: the volume
  * pod's reason as before, or the reason naming the 8191 limit and its pod).  k_spread, sweeps, the
- * split grid, the node axis and the service grid refuse such pods whatever the option says. */
+ * split grid, the node axis and the service grid refuse such pods whatever the option says.  The
+ * option "table_images" changes nothing here: with or without the shape table the kernel is
+ * k_simple. */
 int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3);
 /* The same with the profile the batch runs under (NULL: kss_plan_podset): a profile with
  * percentageOfNodesToScore below 100 on a cluster of 100+ nodes (the findNodesThatPassFilters
@@ -933,7 +943,10 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
  * (ps->n_pods entries) counts from 0 in order of first appearance, *n = the shape count.  Two pods
  * share a shape when their NodeResourcesFit request, LeastAllocated and BalancedAllocation
  * requests (cpu, memory, ephemeral-storage) and "every request is zero" agree exactly; n_scalar:
- * the cluster's extended resources.  KSS_E_UNSUPPORTED when the batch has no compact records. */
+ * the cluster's extended resources.  KSS_E_UNSUPPORTED when the batch has no compact records.
+ * Follows the process-wide option "simple_ports_images" as kss_plan_podset does: with 1, a batch
+ * whose pods hold host ports or node-cached images has records (of the ports-and-images form) and
+ * its shapes are returned -- ports and images are no part of a shape; with 0 it is refused. */
 int kss_plan_shapes(const kss_podset* ps, int32_t n_scalar, int32_t* ids, int32_t* n);
 const char* kss_plan_reason(int32_t code);
 /* Test support: y[i] = the device restatement of Go math.Log (kss_spread.cuh go_log_dev,

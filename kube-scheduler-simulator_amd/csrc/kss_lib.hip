@@ -24,6 +24,9 @@
 //                and statistics, one sweep over shards x waves entries replaces the in-shard
 //                reduction followed by the cross-shard one (simple_sync_flat;
 //                flat_exchange_ok decides, option flat_exchange).
+//   k_simple_tab_pi, k_simple_tab_flat_pi  the two table kernels for an image-only batch of the
+//                ports-and-images form: k_static_pi's words, ImageLocality added to the key
+//                (options simple_ports_images and table_images; no pod holds a host port).
 //   k_spread    the sequential loop of batches WITH spread / inter-pod-affinity programs
 //                (no result record): node rows, label ids, the pod's count rows and
 //                the launch's commits in LDS, host-resolved pod programs (GPod),
@@ -77,7 +80,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_N
 };
 struct OptDef {
   const char* name;
@@ -116,6 +119,7 @@ const OptDef kOptDefs[O_N] = {
     {"shape_table", "KSS_SHAPE_TABLE", 1},                // k_simple's shape table: 1 sharded grids that admit it, 2 also one shard, 0 never
     {"flat_exchange", "KSS_FLAT_EXCHANGE", 1},            // the shape-table loop's exchange: 1 every wave publishes (one sweep), 0 two-level
     {"simple_ports_images", "KSS_SIMPLE_PORTS_IMAGES", 0},  // k_simple's ports-and-images form for NodePorts / ImageLocality pods
+    {"table_images", "KSS_TABLE_IMAGES", 0},                // that form's batches without a host-port pod on the shape-table loop
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -409,8 +413,8 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab(const DevJob* __
   const DevJob job = jobs[ji];
   unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
   const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
-  simple_schedule_tab<false>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w, cap, g,
-                             X, epoch0, err, ji == 0 ? stamps : nullptr, smem, n_shapes);
+  simple_schedule_tab<false, false>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w,
+                                    cap, g, X, epoch0, err, ji == 0 ? stamps : nullptr, smem, n_shapes);
 }
 
 // k_simple_tab with the flat exchange (simple_sync_flat); defined at the end of this file, behind
@@ -418,6 +422,14 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab(const DevJob* __
 __global__ void k_simple_tab_flat(const DevJob* __restrict__ jobs, kss_profile prof, int W, int cap, int k0, int k1,
                                   unsigned long long* gran, int* err, unsigned long long* stamps, XPeers X,
                                   unsigned epoch0, int stat_row0, int n_shapes);
+// ... and the two for an image-only batch of the ports-and-images form, behind it: every kernel
+// that was there keeps its place in the code object
+__global__ void k_simple_tab_pi(const DevJob* __restrict__ jobs, kss_profile prof, int W, int cap, int k0, int k1,
+                                unsigned long long* gran, int* err, unsigned long long* stamps, XPeers X,
+                                unsigned epoch0, int stat_row0, int n_shapes);
+__global__ void k_simple_tab_flat_pi(const DevJob* __restrict__ jobs, kss_profile prof, int W, int cap, int k0, int k1,
+                                     unsigned long long* gran, int* err, unsigned long long* stamps, XPeers X,
+                                     unsigned epoch0, int stat_row0, int n_shapes);
 
 // grid = W (one cluster); each shard's nodes live in LDS (cap slots); bins_cap: histogram +
 // presence values of the exchange vector.  DEF: the v1.26 default profile, folded.  FOLD: the
@@ -938,6 +950,7 @@ struct kss_ctx {
   // the ports-and-images form (option simple_ports_images): the staged batch holds a NodePorts /
   // ImageLocality pod and k_simple_pi takes it; the pods' port masks beside their records
   bool spod_pi = false;
+  bool spod_ports = false;  // ... and some pod of it holds a host port (no shape table: UsedPorts is loop state)
   DevBuf sport_buf;
   std::vector<SPort> sport_host;
   bool staged_names = false;  // some staged pod has a NodeAffinity PreFilterResult node list
@@ -3037,7 +3050,9 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
                          hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
                          int n_shapes = 0, bool flat = false, const SPort* sports = nullptr) {
-  const bool pi = sports != nullptr;  // the ports-and-images form (one job): k_static_pi + k_simple_pi
+  // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
+  // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
+  const bool pi = sports != nullptr;
   // st2 (with pev, two events per chunk): the static words of chunk i+1 are computed on st2 into the
   // other half of a double-buffered table while k_simple runs chunk i on st (each job's table holds
   // 2 x chunk rows); k_simple of chunk i waits for its k_static, k_static of chunk i+1 for
@@ -3048,16 +3063,15 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   // launch with the same nextStartNodeIndex in its own cursor word, simple_schedule)
   const bool win = k_find > 0;
   // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
-  // (pi: no shape table)
-  const bool tab = n_shapes > 0 && def && !win && nsc == 0 && !pi;
-  const size_t shmem = pi ? simple_lds_bytes_pi(cap, nsc) : simple_lds_bytes(cap, nsc, tab ? n_shapes : 0);
+  const bool tab = n_shapes > 0 && def && !win && nsc == 0;
+  const size_t shmem = tab ? simple_lds_bytes(cap, 0, n_shapes) : pi ? simple_lds_bytes_pi(cap, nsc) : simple_lds_bytes(cap, nsc);
   // flat: the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
   flat = flat && tab && n_jobs == 1 && !(split && split->X.n > 1);
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
   if (flat && gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
     return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
-  const void* fn = flat  ? (const void*)k_simple_tab_flat
-                   : tab ? (const void*)k_simple_tab
+  const void* fn = flat  ? (pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat)
+                   : tab ? (pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab)
                    : pi  ? (win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
                                 : (def ? (const void*)k_simple_pi<true, false> : (const void*)k_simple_pi<false, false>))
                    : win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
@@ -3628,7 +3642,10 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   ctx->last_xcd[0] = (simple && xcd_try && g.W > 1) || xcd_spread ? 1 : 0;
   ctx->last_xcd[1] = 0;
   // the shape table: the whole staged batch (its shape directory sits in its first records)
-  const bool tab = simple && !simple_pi && opt(O_SHAPE_TABLE) && n == ctx->staged_n &&
+  // (the ports-and-images form: an image-only batch, option table_images -- k_simple_tab_pi;
+  // UsedPorts is not a function of the resource shape, so a host-port pod keeps the batch on k_simple_pi)
+  const bool tab = simple && (!simple_pi || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
+                   n == ctx->staged_n &&
                    shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
   ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;
   ctx->last_shape[1] = tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
@@ -3767,6 +3784,8 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   PiRecords pi;
   ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi);
   ctx->spod_pi = ctx->spod_ok && pi.form;
+  ctx->spod_ports = false;
+  for (const SPort& q : pi.ports) ctx->spod_ports |= (q.conflict | q.add) != 0;
   ctx->sport_host.swap(pi.ports);
   ctx->gpod_ok = false;
   if (!ctx->spod_ok) {  // programs: the resolved records of k_spread
@@ -4802,7 +4821,8 @@ int kss_plan_shapes(const kss_podset* ps, int32_t n_scalar, int32_t* ids, int32_
     return fail(KSS_E_INVAL, "bad arguments");
   std::vector<SPod> sp;
   int ns = 0;
-  if (!build_spods(ps, n_scalar, sp, &ns)) return fail(KSS_E_UNSUPPORTED, "the batch has no compact records (k_simple does not take it)");
+  PiRecords pi;  // (follows the process-wide option simple_ports_images, as kss_plan_podset)
+  if (!build_spods(ps, n_scalar, sp, &ns, &pi)) return fail(KSS_E_UNSUPPORTED, "the batch has no compact records (k_simple does not take it)");
   for (int i = 0; i < ps->n_pods; i++) ids[i] = sp[(size_t)i].shape;
   *n = ns;
   return 0;
@@ -5613,6 +5633,46 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab_flat(const DevJo
   if (w >= W) return;
   const DevJob job = jobs[0];
   const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
-  simple_schedule_tab<true>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w, cap,
-                            gran, X, epoch0, err, stamps, smem, n_shapes);
+  simple_schedule_tab<true, false>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w,
+                                   cap, gran, X, epoch0, err, stamps, smem, n_shapes);
+}
+
+// k_simple_tab for an image-only batch of the ports-and-images form (simple_schedule_tab<.., PI = true>:
+// k_static_pi's words, ImageLocality in the key).  A kernel of its own beside k_simple_tab, restating
+// its body, so that kernel keeps its code; launched only with the options simple_ports_images and
+// table_images on, for a batch without a host-port pod.
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab_pi(const DevJob* __restrict__ jobs, kss_profile prof, int W,
+                                                                   int cap, int k0, int k1, unsigned long long* gran,
+                                                                   int* err, unsigned long long* stamps, XPeers X,
+                                                                   unsigned epoch0, int stat_row0, int n_shapes) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  const int Wl = X.n > 1 ? X.wl : W;
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  int xs = 0;  // as k_simple
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return 2 * (size_t)W * SX_VALS; }, W, err)) < 0) return;
+  const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
+  const DevJob job = jobs[ji];
+  unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  simple_schedule_tab<false, true>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w,
+                                   cap, g, X, epoch0, err, ji == 0 ? stamps : nullptr, smem, n_shapes);
+}
+
+// k_simple_tab_flat for an image-only batch of the ports-and-images form (k_simple_tab_pi's words).
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab_flat_pi(const DevJob* __restrict__ jobs, kss_profile prof,
+                                                                        int W, int cap, int k0, int k1,
+                                                                        unsigned long long* gran, int* err,
+                                                                        unsigned long long* stamps, XPeers X,
+                                                                        unsigned epoch0, int stat_row0, int n_shapes) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const size_t gw = 2 * (size_t)W * (blockDim.x >> 6) * SXF_VALS;
+  int xs = 0;  // as k_simple
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return gw; }, W, err)) < 0) return;
+  const int w = X.xcd_local ? xs : (int)blockIdx.x;
+  if (w >= W) return;
+  const DevJob job = jobs[0];
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  simple_schedule_tab<true, true>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w,
+                                  cap, gran, X, epoch0, err, stamps, smem, n_shapes);
 }

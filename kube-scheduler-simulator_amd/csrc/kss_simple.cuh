@@ -238,7 +238,7 @@ __device__ __forceinline__ int sw_code(uint32_t w) {
 __device__ __forceinline__ int sw_tt(uint32_t w) { return (int)((w >> 5) & 0x7Fu); }
 __device__ __forceinline__ int sw_na(uint32_t w) { return (int)(w >> 12); }
 
-// The ports-and-images form (PI: k_static_pi, k_simple_pi) of the static word: raw
+// The ports-and-images form (PI: k_static_pi, k_simple_pi, k_simple_tab_pi) of the static word: raw
 // NodeAffinity narrows to 13 bits (bits 12-24; host-checked: every pod's Σ positive preferred
 // weights <= SWPI_NA_MAX) and bits 25-31 hold the ImageLocality score (0..100; final, it has no
 // NormalizeScore); both 0 unless bits 0-2 are 0.  The other fields are where they were.
@@ -2476,7 +2476,14 @@ __device__ __forceinline__ bool simple_sync_flat(SimpleHdr& H, int& parity, long
 // Sharing them as inline helpers changed the code of all five loop kernels (more SGPR spill
 // traffic) and cost C1 8.6 %, pct 0 0.9 %, C2 0.3 %: profiles/r10b_loop_pieces_ab.txt.  A change
 // to one of these pieces is made in both loops.
-template <bool FLAT>
+// PI (k_simple_tab_pi, k_simple_tab_flat_pi): an image-only batch of the ports-and-images form.
+// The static words are k_static_pi's (SWPI_*): raw NodeAffinity in 13 bits, the ImageLocality
+// score above it.  ImageLocality is static and has no NormalizeScore, so it is no loop state: pass B
+// adds il x weight to the key's total field (pi_key_add's term) and the statistics mask the
+// NodeAffinity field; T, the refresh, pnd, the commit, the rings and the ordering above are the
+// same.  No pod of such a batch holds a host port (the host checks it), so there is no UsedPorts
+// column and no SPort ring in LDS, and the port column in HBM is neither read nor written.
+template <bool FLAT, bool PI>
 __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __restrict__ spods,
                                                     const uint32_t* __restrict__ stat, int k0, int k1, int n_pods,
                                                     int32_t* chosen, PodMeta* meta, int W, int w, int cap,
@@ -2642,8 +2649,13 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
     const float rna = __builtin_amdgcn_rcpf((float)max(max_na, 1));
     long long best = 0;
     {
-      const SVal e{sw_code(a_w), sw_tt(a_w), sw_na(a_w), (int)((a_t >> 8) & 0xFFu), (int)(a_t & 0xFFu)};
-      const long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s));
+      const int a_na = PI ? (int)((uint32_t)sw_na(a_w) & SWPI_NA_MAX) : sw_na(a_w);
+      const SVal e{sw_code(a_w), sw_tt(a_w), a_na, (int)((a_t >> 8) & 0xFFu), (int)(a_t & 0xFFu)};
+      long long key = simple_key(prof, e, scored, max_tt, rtt, max_na, rna, (uint32_t)(c.node_base + lo + s));
+      if constexpr (PI) {  // ImageLocality: its raw score is final; unsigned (il = 100 sets bit 31 of the word)
+        const uint32_t il = a_w >> SWPI_IL_SHIFT;
+        key += scored ? (long long)((unsigned long long)(il * (uint32_t)prof.weight[KSS_S_IMAGE_LOCALITY]) << 32) : 0ll;
+      }
       best = (keys && mine && e.f == 0 && (a_t & ST_FITS)) ? key : 0;
     }
     if (sp && tid == 0) sp[1] = wall_clock64();
@@ -2676,7 +2688,7 @@ __device__ __forceinline__ void simple_schedule_tab(DevCluster c, const SPod* __
       }
       ok &= sw_code(wd) == 0;
       const bool c0 = ok && !extra, c1 = ok && (extra || s != cand);
-      const uint32_t tt = (uint32_t)sw_tt(wd), na = (uint32_t)sw_na(wd);
+      const uint32_t tt = (uint32_t)sw_tt(wd), na = PI ? ((uint32_t)sw_na(wd) & SWPI_NA_MAX) : (uint32_t)sw_na(wd);
       u[0] = c0 ? 1u : 0u;
       u[1] = c0 ? tt : 0u;
       u[2] = c0 ? na : 0u;

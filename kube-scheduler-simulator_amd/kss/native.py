@@ -676,7 +676,8 @@ class Context:
 
     def last_shape_table(self) -> Dict[str, int]:
         """{shapes, rounds} of k_simple's shape table in the last run (kss_last_shape_table);
-        shapes 0: the batch ran without the table."""
+        shapes 0: the batch ran without the table.  An image-only batch of the ports-and-images form
+        (options simple_ports_images and table_images both 1) is reported like any table run."""
         out = (C.c_int32 * 2)()
         check(lib().kss_last_shape_table(self.h, out))
         return {"shapes": out[0], "rounds": out[1]}
@@ -799,7 +800,9 @@ def device_go_log(x, device: int = 0) -> np.ndarray:
 
 def plan_shapes(podset: abi.PodSet, n_scalar: int = 0):
     """Host-only: (ids, n) -- the resource shape id of every pod as a staged batch numbers them
-    (first appearance order) and the shape count (kss_plan_shapes)."""
+    (first appearance order) and the shape count (kss_plan_shapes).  Follows the option
+    simple_ports_images as plan_podset does: with 1 a batch whose pods hold host ports or name
+    node-cached images has shapes, with 0 it raises KssError (-95)."""
     n_pods = int(podset.n_pods)
     ids = np.zeros(max(n_pods, 1), dtype=np.int32)
     n = C.c_int32(0)
