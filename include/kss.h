@@ -467,7 +467,13 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * "table_images" (default 0; effective only with "simple_ports_images" 1: a batch of that form in
  * which no pod holds a host port runs on the shape-table loop, kss_last_shape_table, under that
  * loop's own conditions; a batch with a host-port pod, the window, a runtime profile, one shard with
- * "shape_table" 1 and more than KSS_MAX_SHAPES shapes run as with 0).  Read when a context is created (shards, xcd, xcd_shards,
+ * "shape_table" 1 and more than KSS_MAX_SHAPES shapes run as with 0), "spread_ports_images"
+ * (default 0, independent of "simple_ports_images"; 1: a staged, unrecorded batch WITH spread /
+ * inter-pod programs and without volumes whose pods hold host ports or node-cached images runs on
+ * k_spread's ports-and-images form instead of k_schedule -- on one part, with "fold" 0 and an empty
+ * nominator, chunked launches and the window included -- provided every pod's preferred NodeAffinity
+ * weights sum to at most 8191; batches without such pods are routed and launched as with 0;
+ * kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -797,6 +803,11 @@ int kss_buffer_map(kss_ctx* ctx, uint64_t* base, uint64_t* bytes, int32_t cap, i
 /* launch geometry of the last scheduling launch: out[0] shards (workgroups) per cluster,
  * out[1] threads per workgroup, out[2] node slots per lane */
 int kss_last_geometry(kss_ctx* ctx, int32_t* out3);
+/* LDS bytes per workgroup of the last batch's k_spread launches, without the diagnostic stamps
+ * (0: the batch ran on another kernel).  The ports-and-images form (option "spread_ports_images")
+ * adds 8 bytes per node slot, the UsedPorts column, and one uint4 to each of the three staged
+ * records; a batch without a host-port / image pod asks the same with the option on and off. */
+int kss_last_spread_lds(kss_ctx* ctx, int64_t* bytes);
 /* XCD-local grid of the last run: out2[0] = 1 when its k_simple shards ran on one XCD (the
  * per-pod exchange in that XCD's L2: a cluster of at most CUs-per-XCD shards, one node per lane;
  * KSS_XCD=0 disables it), out2[1] = the chunks that found fewer workgroups on that XCD than shards
@@ -928,8 +939,11 @@ int kss_abi_sizes(int32_t* out, int32_t n);
  * ..."), unless the process-wide option "simple_ports_images" is 1; then the batch is planned on
  * k_simple (its ports-and-images form) when it has no spread / inter-pod program and no volume and
  * every pod's Σ positive preferred NodeAffinity weights is <= 8191 (else k_schedule: the volume
- * pod's reason as before, or the reason naming the 8191 limit and its pod).  k_spread, sweeps, the
- * split grid, the node axis and the service grid refuse such pods whatever the option says.  The
+ * pod's reason as before, or the reason naming the 8191 limit and its pod).  A batch of such pods
+ * WITH spread / inter-pod programs follows the option "spread_ports_images" instead: 1 plans it on
+ * k_spread (its ports-and-images form) under the same two conditions and with the option "fold" 0
+ * (the 8191 limit has a reason of its own there, naming k_spread).  Sweeps, the split grid, the node
+ * axis and the service grid refuse such pods whatever the options say.  The
  * option "table_images" changes nothing here: with or without the shape table the kernel is
  * k_simple. */
 int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3);

@@ -31,6 +31,8 @@
 //                (no result record): node rows, label ids, the pod's count rows and
 //                the launch's commits in LDS, host-resolved pod programs (GPod),
 //                32-bit exchanges (kss_spread.cuh).
+//                With the option spread_ports_images its PI instantiations take NodePorts /
+//                ImageLocality pods too: k_static_pi's words, a UsedPorts column in LDS.
 //   k_commit     one lane: AssumePod / ForgetPod delta on one node row.
 //   k_preempt    one workgroup: the DefaultPreemption PostFilter dry run of one pod
 //                (kss_preempt.cuh).
@@ -80,7 +82,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_N
 };
 struct OptDef {
   const char* name;
@@ -120,6 +122,7 @@ const OptDef kOptDefs[O_N] = {
     {"flat_exchange", "KSS_FLAT_EXCHANGE", 1},            // the shape-table loop's exchange: 1 every wave publishes (one sweep), 0 two-level
     {"simple_ports_images", "KSS_SIMPLE_PORTS_IMAGES", 0},  // k_simple's ports-and-images form for NodePorts / ImageLocality pods
     {"table_images", "KSS_TABLE_IMAGES", 0},                // that form's batches without a host-port pod on the shape-table loop
+    {"spread_ports_images", "KSS_SPREAD_PORTS_IMAGES", 0},  // k_spread's ports-and-images form (independent of simple_ports_images)
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -440,7 +443,9 @@ __global__ void k_simple_tab_flat_pi(const DevJob* __restrict__ jobs, kss_profil
 // allocator keeps in registers what the 512-lane bound spills to scratch.
 // WIN: percentageOfNodesToScore < 100 (one job): k_find = numFeasibleNodesToFind, the window's
 // nextStartNodeIndex in job.cursor (kss_spread.cuh spread_schedule)
-template <bool DEF, bool FOLD, int LB, bool WIN>
+// PI: the ports-and-images form (option spread_ports_images; spread_schedule PI), instantiated at
+// the end of this file (spread_pi_fn), behind every other kernel.
+template <bool DEF, bool FOLD, int LB, bool WIN, bool PI = false>
 __global__ __launch_bounds__(LB) void k_spread(const DevJob* __restrict__ jobs, int W, int cap, int bins_cap,
                                                             int n_res, int gq, int gs, int k0, int k1, unsigned long long* gran,
                                                             int* err, unsigned long long* stamps, int nst, XPeers X,
@@ -459,7 +464,7 @@ __global__ __launch_bounds__(LB) void k_spread(const DevJob* __restrict__ jobs, 
   constexpr kss_profile def_prof = default_profile_c();
   if (!DEF) stage_profile(H, jobs[ji].prof);
   const kss_profile& P = DEF ? def_prof : H.prof;
-  spread_schedule<DEF, FOLD, WIN>(job.trace, job.c, job.gpods, job.stat, job.res_rows, n_res, k0, min(k1, job.n_pods), job.chosen, job.meta, P, W, w,
+  spread_schedule<DEF, FOLD, WIN, PI>(job.trace, job.c, job.gpods, job.stat, job.res_rows, n_res, k0, min(k1, job.n_pods), job.chosen, job.meta, P, W, w,
                   cap, bins_cap, gq, gs, gran ? gran + (size_t)ji * 2 * W * gs : nullptr, X, epoch0, err, stamps, nst, hc,
                   smem, k_find, job.cursor);
 }
@@ -482,6 +487,10 @@ __global__ __launch_bounds__(256) void k_handoff_final(const DevJob* __restrict_
   const DevJob& job = jobs[0];
   handoff_final_check(job.c, job.res_rows, n_res, W, w_off + (int)blockIdx.x, hc, err, scratch);
 }
+// ... and of the ports-and-images form (the UsedPorts column in the sum), with that form's k_spread
+// instantiations (spread_pi_fn) at the end of this file
+__global__ void k_handoff_final_pi(const DevJob* __restrict__ jobs, int W, int w_off, int n_res, HandoffCheck hc, int* err);
+static const void* spread_pi_fn(bool def, bool lb, bool win);
 
 // Static words of pods [k0, min(k1, n_pods)) x every node of every job.  grid: x = 1024-node
 // tiles, y = groups of STATIC_PODS pods, z = job.  One lane per QUAD of adjacent nodes walks its
@@ -843,6 +852,7 @@ struct GpodNeeds {
   int soft_xw = 0;        // max soft presence bins of a pod (its own E2)
   int gs() const { return (xw + 15) / 16 * 16; }  // granule stride per shard: whole 128-byte lines
   int fail_code = 0, fail_pod = -1;  // why / where build_gpods refused (GP_*)
+  bool pi = false;        // records of the ports-and-images form (option spread_ports_images): an SPort ends each
 };
 
 // Per-batch LDS / exchange sizing: the host restatement of make_plan's bin counts.
@@ -938,6 +948,7 @@ struct kss_ctx {
   int pref_threads = 256;     // KSS_THREADS
   PlanNeeds staged_need;
   int last_geom[3] = {0, 0, 0};
+  long long last_lds = 0;  // dynamic LDS bytes per workgroup of the last k_spread launch (0: another kernel)
   bool stream_dedicated = false;      // `stream` has a hardware queue of its own (split parts: dedicated_stream)
   const char* stamps_file = nullptr;  // kss_set_stamps_file: dump per-phase timestamps of each launch
   std::string stamps_path;
@@ -958,6 +969,7 @@ struct kss_ctx {
   DevBuf gpod_buf;
   std::vector<uint4> gpod_host;  // records, gneed.gq uint4 each
   bool gpod_ok = false;
+  bool gpod_pi = false;  // ... of the ports-and-images form (option spread_ports_images; GpodNeeds::pi)
   GpodNeeds gneed;
   bool no_spread = false;     // KSS_NO_SPREAD: batches with programs always take k_schedule
   double count_bound0 = 0;    // max(Σ class_count, Σ term_count) of the loaded snapshot
@@ -1394,6 +1406,7 @@ enum {
   GP_PCT,
   GP_SCALAR_SCORED,
   GP_PI_NA_WEIGHTS,
+  GP_SPREAD_PI_NA_WEIGHTS,
   GP_NCODES
 };
 const char* const kGpReason[GP_NCODES] = {
@@ -1416,6 +1429,8 @@ const char* const kGpReason[GP_NCODES] = {
     "the profile scores an extended (scalar) resource and the cluster has extended resources: k_schedule only",
     "preferred NodeAffinity weights above 8191 in a batch with host ports or node-cached images (k_simple's "
     "ports-and-images form keeps 13 bits of raw NodeAffinity): k_schedule only",
+    "preferred NodeAffinity weights above 8191 in a batch with programs and host ports or node-cached images "
+    "(k_spread's ports-and-images form keeps 13 bits of raw NodeAffinity): k_schedule only",
 };
 
 bool gfail(GpodNeeds& need, int code, int pod) {
@@ -1424,11 +1439,19 @@ bool gfail(GpodNeeds& need, int code, int pod) {
   return false;
 }
 
+// The ports-and-images form (option spread_ports_images on and some pod with host ports or image
+// rows: need.pi): such pods are admitted, every record is of that form (fill_spod's 13-bit limit
+// on raw NodeAffinity) and ends in the pod's SPort, one uint4 behind the longest reference list.
+// A batch without such a pod is built exactly as with the option off.
 bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_t* key_card, const uint32_t* key_flags,
                  const int32_t* key_empty, std::vector<uint4>& words, GpodNeeds& need) {
   std::vector<GPod> out((size_t)std::max(ps->n_pods, 1), GPod{});
   std::vector<std::vector<uint32_t>> refs_of((size_t)std::max(ps->n_pods, 1));
   need = GpodNeeds{};
+  bool pi = false;
+  if (opt(O_SPREAD_PI) && !opt(O_FOLD))  // (no PI instantiation of the statistics fold)
+    for (int i = 0; i < ps->n_pods; i++) pi |= pod_ports_images(ps->pods[i]);
+  need.pi = pi;
   std::vector<int32_t> local;  // count row -> resident index (-1 none)
   auto res_of = [&](int rowid) -> int {
     if ((size_t)rowid >= local.size()) local.resize((size_t)rowid + 1, -1);
@@ -1442,8 +1465,12 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     const kss_pod& p = ps->pods[i];
     GPod& g = out[(size_t)i];
     std::vector<uint32_t>& R = refs_of[(size_t)i];
-    if (p.port_conflict | p.port_add || p.img_len > 0 || p.vol_len > 0) return gfail(need, GP_PORTS_IMAGES, i);
-    if (!fill_spod(ps, p, n_scalar, g.dyn)) return gfail(need, GP_NA_WEIGHTS, i);
+    if ((!pi && pod_ports_images(p)) || p.vol_len > 0) return gfail(need, GP_PORTS_IMAGES, i);
+    if (!fill_spod(ps, p, n_scalar, g.dyn, pi)) {
+      int64_t wsum = 0;  // the form's own limit, or weights no static word holds
+      for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
+      return gfail(need, pi && wsum <= 0xFFFFF ? GP_SPREAD_PI_NA_WEIGHTS : GP_NA_WEIGHTS, i);
+    }
     if (p.n_hard > MAXH || p.n_soft > MAXS) return gfail(need, GP_CONSTRAINTS, i);
     g.pflags = (int32_t)p.flags;
     g.n_hard = p.n_hard;
@@ -1661,7 +1688,7 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     }
   }
   // records: header + references, one stride of gq uint4 each
-  const size_t gq = (sizeof(GPod) + 4 * rmax + 15) / 16;
+  const size_t gq = (sizeof(GPod) + 4 * rmax + 15) / 16 + (pi ? 1 : 0);  // pi: the SPort, the record's last uint4
   if (gq > (size_t)G_QMAX) return gfail(need, GP_RECORD, rmax_pod);
   need.gq = (int)gq;
   words.assign(gq * out.size(), uint4{0, 0, 0, 0});
@@ -1669,6 +1696,10 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     char* rec = reinterpret_cast<char*>(words.data() + i * gq);
     std::memcpy(rec, &out[i], sizeof(GPod));
     if (!refs_of[i].empty()) std::memcpy(rec + sizeof(GPod), refs_of[i].data(), 4 * refs_of[i].size());
+    if (pi && i < (size_t)ps->n_pods) {
+      const SPort sp{ps->pods[i].port_conflict, ps->pods[i].port_add};
+      std::memcpy(rec + 16 * (gq - 1), &sp, sizeof(SPort));
+    }
   }
   return true;
 }
@@ -3171,7 +3202,7 @@ static int spread_cap(const Geometry& g, size_t N) {
 }
 
 static size_t spread_lds(const Geometry& g, const GpodNeeds& q, int n_keys, int n_res, size_t N, int nsc) {
-  return spread_lds_bytes(spread_cap(g, N), q.bins_cap, n_keys, n_res, q.gq, nsc, opt(O_FOLD) != 0);
+  return spread_lds_bytes(spread_cap(g, N), q.bins_cap, n_keys, n_res, q.gq, nsc, opt(O_FOLD) != 0, q.pi);
 }
 
 static bool spread_fits(const Geometry& g, const GpodNeeds& q, int n_keys, int n_res, size_t N, int nsc) {
@@ -3185,11 +3216,11 @@ static bool spread_fits(const Geometry& g, const GpodNeeds& q, int n_keys, int n
 // each shard's last epilogue (int), the diagnosis list, the shadow copy of the node state.
 struct HandoffLayout {
   size_t o_xcc, o_diag, o_shadow, words;
-  HandoffLayout(int W, int n_res, int N, int nsc) {
+  HandoffLayout(int W, int n_res, int N, int nsc, bool pi = false) {  // pi: the UsedPorts column behind the scalar columns
     o_xcc = 2 * (size_t)W;
     o_diag = o_xcc + ((size_t)W + 1) / 2;
     o_shadow = (o_diag + 1 + (size_t)HANDOFF_DIAG * HANDOFF_DIAG_W + 15) / 16 * 16;
-    words = o_shadow + (6 + (size_t)std::max(n_res, 0) + (size_t)std::max(nsc, 0)) * (size_t)std::max(N, 1);
+    words = o_shadow + (6 + (size_t)std::max(n_res, 0) + (size_t)std::max(nsc, 0) + (pi ? 1 : 0)) * (size_t)std::max(N, 1);
   }
 };
 
@@ -3226,6 +3257,12 @@ static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, 
     if (!def || fold) return fail(KSS_E_INVAL, "k_spread window: default profile, no statistics fold");
     fn = lb ? (const void*)k_spread<true, false, 256, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, true>;
   }
+  // the ports-and-images form (build_gpods need.pi; run_single checked: one part, no fold): its own
+  // instantiations, and k_static_pi's words
+  if (q.pi) {
+    if (fold || split) return fail(KSS_E_INVAL, "k_spread ports-and-images form: one part, no statistics fold");
+    fn = spread_pi_fn(def, lb, k_find > 0);
+  }
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   XPeers X = split ? split->X : XPeers{};
   const bool sp_grid = X.n > 1;
@@ -3243,7 +3280,7 @@ static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, 
   static_rows(g, X, max_nodes, n_lo, n_hi);
   for (int k0 = 0; k0 < n_pods; k0 += chunk) {
     int k1 = std::min(n_pods, k0 + chunk);
-    launch_static(st, def, jobs, pr, 1, k0, k1, n_lo, n_hi, n_keys);
+    launch_static(st, def, jobs, pr, 1, k0, k1, n_lo, n_hi, n_keys, 0, q.pi);
     HIP_TRY(hipGetLastError());
     // every chunk's tags above the previous chunk's (a line an earlier chunk left in an XCD's
     // L2 never carries a current tag), the buffer zeroed as well
@@ -3260,7 +3297,7 @@ static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, 
     // over the context's life, the first chunk of a call checks nothing
     HandoffCheck hc{};
     if (ck && ck_seq) {
-      const HandoffLayout hl(g.W, n_res, max_nodes, nsc);
+      const HandoffLayout hl(g.W, n_res, max_nodes, nsc, q.pi);
       hc.sum = ck;
       hc.expect = k0 > 0 ? *ck_seq : 0ull;
       hc.write = ++*ck_seq;
@@ -3296,7 +3333,7 @@ static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, 
     if (ev) HIP_TRY(hipEventRecord(ev[2 * ci + 1], st));
   }
   if (ck && ck_seq && n_pods > 0) {  // the last chunk's write-back, checked (nothing repairs it)
-    const HandoffLayout hl(g.W, n_res, max_nodes, nsc);
+    const HandoffLayout hl(g.W, n_res, max_nodes, nsc, q.pi);
     HandoffCheck hc{};
     hc.sum = ck;
     hc.expect = *ck_seq;
@@ -3304,7 +3341,8 @@ static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, 
     hc.xcc = (int*)(ck + hl.o_xcc);
     hc.diag = (long long*)(ck + hl.o_diag);
     hc.shadow = (long long*)(ck + hl.o_shadow);
-    hipLaunchKernelGGL(k_handoff_final, grid, dim3(256), 0, st, jobs, W, sp_grid ? X.w_off : 0, n_res, hc, err);
+    if (q.pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, jobs, W, sp_grid ? X.w_off : 0, n_res, hc, err);
+    else hipLaunchKernelGGL(k_handoff_final, grid, dim3(256), 0, st, jobs, W, sp_grid ? X.w_off : 0, n_res, hc, err);
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -3420,7 +3458,9 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   const bool spread_ok = spread_win_ok && !nomq && staged && ctx->gpod_ok && commit && !record && !keep_norm && need.general &&
                          scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
                          !ctx->no_simple && !ctx->no_spread && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
-                         spread_bounds_ok(ctx->gneed, count_total, cell_total, (int)N);
+                         spread_bounds_ok(ctx->gneed, count_total, cell_total, (int)N) &&
+                         // the ports-and-images form: one part, no fold, and the option still on (it is process-wide)
+                         (!ctx->gpod_pi || (!split && opt(O_SPREAD_PI) && !opt(O_FOLD)));
   if (opt(O_TRACE_PATH))  // diagnosis: why a batch with programs is (not) on k_spread
     fprintf(stderr,
             "kss path: staged=%d gpod_ok=%d commit=%d record=%d general=%d scalar=%d small=%d f64=%d bounds=%d "
@@ -3640,6 +3680,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
     ctx->loop_ev.push_back(e);
   }
   ctx->last_xcd[0] = (simple && xcd_try && g.W > 1) || xcd_spread ? 1 : 0;
+  ctx->last_lds = 0;
   ctx->last_xcd[1] = 0;
   // the shape table: the whole staged batch (its shape directory sits in its first records)
   // (the ports-and-images form: an image-only batch, option table_images -- k_simple_tab_pi;
@@ -3659,7 +3700,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
                        simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr);
   else if (spread)
   {
-    const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar);
+    const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi);
     if ((rc = ctx->ck_buf.ensure(sizeof(unsigned long long) * hl.words))) return rc;
     HIP_TRY(dev_zero((unsigned long long*)ctx->ck_buf.p + hl.o_diag, sizeof(unsigned long long), ctx->stream));
     ctx->ck_diag_off = hl.o_diag;
@@ -3669,6 +3710,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
       qw.bins_cap += g.W;
       qw.xw = std::max(qw.xw, g.W + 1);
     }
+    ctx->last_lds = (long long)spread_lds(g, qw, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar);
     rc = launch_spread(ctx->stream, g, qw, ctx->dc.n_keys, n_res, jd, ctx->prof, n,
                        (int)N, chunk, gran, gb, errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr,
                        (unsigned long long*)ctx->ck_buf.p, &ctx->ck_seq, ctx->dc.n_scalar, xcd_spread, &ctx->last_xcd[1],
@@ -3787,11 +3829,12 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   ctx->spod_ports = false;
   for (const SPort& q : pi.ports) ctx->spod_ports |= (q.conflict | q.add) != 0;
   ctx->sport_host.swap(pi.ports);
-  ctx->gpod_ok = false;
+  ctx->gpod_ok = ctx->gpod_pi = false;
   if (!ctx->spod_ok) {  // programs: the resolved records of k_spread
     ctx->gpod_ok = build_gpods(ps, ctx->dc.n_scalar, ctx->dc.n_classes, ctx->key_card_h.data(), ctx->key_flags_h.data(),
                                ctx->key_empty_h.data(), ctx->gpod_host, ctx->gneed);
     if (!ctx->gpod_ok) return 0;
+    ctx->gpod_pi = ctx->gneed.pi;
     int rc = ctx->gpod_buf.ensure(sizeof(uint4) * ctx->gpod_host.size());
     if (rc) return rc;
     if ((rc = ctx->res_buf.ensure(sizeof(int32_t) * std::max<size_t>(ctx->gneed.res_rows.size(), 1)))) return rc;
@@ -4795,6 +4838,12 @@ int kss_last_geometry(kss_ctx* ctx, int32_t* out3) {
   return 0;
 }
 
+int kss_last_spread_lds(kss_ctx* ctx, int64_t* bytes) {
+  if (!ctx || !bytes) return fail(KSS_E_INVAL, "bad arguments");
+  *bytes = ctx->last_lds;
+  return 0;
+}
+
 int kss_last_xcd_local(kss_ctx* ctx, int32_t* out2) {
   if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
   out2[0] = ctx->last_xcd[0];
@@ -5675,4 +5724,23 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_tab_flat_pi(const De
   const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
   simple_schedule_tab<true, true>(job.c, job.spods, stat, k0, min(k1, job.n_pods), job.n_pods, job.chosen, job.meta, W, w,
                                   cap, gran, X, epoch0, err, stamps, smem, n_shapes);
+}
+
+// k_spread's ports-and-images form (option spread_ports_images): the six instantiations with
+// PI = true, {default, runtime profile} x {256, KSS_MAX_THREADS lanes} and the default profile's two
+// window kernels; no statistics fold.  Named here, behind every other kernel, so those keep their places
+// in the code object.
+__global__ __launch_bounds__(256) void k_handoff_final_pi(const DevJob* __restrict__ jobs, int W, int w_off, int n_res,
+                                                          HandoffCheck hc, int* err) {
+  __shared__ long long scratch[4];
+  const DevJob& job = jobs[0];
+  handoff_final_check<true>(job.c, job.res_rows, n_res, W, w_off + (int)blockIdx.x, hc, err, scratch);
+}
+
+static const void* spread_pi_fn(bool def, bool lb, bool win) {
+  if (win)  // (launch_spread refuses a window under a runtime profile before it asks)
+    return lb ? (const void*)k_spread<true, false, 256, true, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, true, true>;
+  if (def)
+    return lb ? (const void*)k_spread<true, false, 256, false, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, false, true>;
+  return lb ? (const void*)k_spread<false, false, 256, false, true> : (const void*)k_spread<false, false, KSS_MAX_THREADS, false, true>;
 }

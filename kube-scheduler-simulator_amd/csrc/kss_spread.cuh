@@ -194,14 +194,17 @@ struct SpreadShard {
 
 // fold (k_spread<., true>): two bins areas (pod k and pod k + 1, by parity) and three static-word
 // slots (pods k .. k + 2: the early statistics pass of pod k + 1 reads its words during pod k)
+// pi (k_spread<.., PI = true>, the ports-and-images form): the UsedPorts column, one uint64 per slot, behind
+// every other array (spread_schedule finds it at the byte count without it)
 __host__ __device__ inline size_t spread_lds_bytes(int cap, int bins_cap, int n_keys, int n_res, int gq, int nsc = 0,
-                                                   bool fold = false) {
+                                                   bool fold = false, bool pi = false) {
   const size_t C = (size_t)cap;
   const size_t nb = (size_t)bins_cap * (fold ? 2 : 1), nst = fold ? 3 : 2;
   size_t b = (sizeof(SpreadHdr) + 4 * ((size_t)G_NS + nb) + 15) / 16 * 16;
   b += 3 * 16 * (size_t)gq + 4 * nst * C + ((size_t)n_res * C * 2 + 15) / 16 * 16;
   b += 8 * 8 * C + 8 * 3 * C + 8 * 2 * C + 4 * 3 * C + 4 * (size_t)n_keys * C + 4 * 6 * C;
   b += 16 * (size_t)nsc * C;
+  if (pi) b += 8 * C;
   return b;
 }
 
@@ -1265,6 +1268,8 @@ __device__ __forceinline__ void handoff_note(const HandoffCheck& hc, int w, int 
 // prologue checks every other hand-off): shard w's node state in HBM summed as the prologue
 // sums it, against the sum and tag its epilogue stored.  A disagreement fails the run (err = 2)
 // and counts in retries[2]; nothing is repaired, so no corrupted write-back passes silently.
+// PI: the ports-and-images form's UsedPorts column, summed behind the scalar columns.
+template <bool PI = false>
 __device__ __forceinline__ void handoff_final_check(const DevCluster& c, const int32_t* __restrict__ res_rows, int n_res,
                                                     int W, int w, const HandoffCheck& hc, int* err, long long* scratch) {
   const size_t N = (size_t)c.N;
@@ -1284,6 +1289,7 @@ __device__ __forceinline__ void handoff_final_check(const DevCluster& c, const i
          handoff_mix((unsigned long long)(uint32_t)ld_ag(&c.pod_count[n]), 5 * N + n);
     for (int i = 0; i < nsc; i++)
       h += handoff_mix((unsigned long long)ld_ag(&c.requested[(size_t)(3 + i) * N + n]), (6 + (size_t)n_res + i) * N + n);
+    if constexpr (PI) h += handoff_mix((unsigned long long)ld_ag(&c.port_used[n]), (6 + (size_t)n_res + nsc) * N + n);
   }
   for (int i = threadIdx.x; i < n_res * own; i += blockDim.x) {
     const int r = i / own, s = i - r * own, row = res_rows[r];
@@ -1504,7 +1510,17 @@ __device__ __forceinline__ int32_t trace_eff(const SpreadShard& L, const GPod& q
 // The batch for shard w of one cluster, pods [k0, k1).  res_rows: the resident count rows
 // (class r as r, term r as n_classes + r), n_res of them.  FOLD: the next pod's statistics ride with
 // this pod's filter exchange and argmax (spread_argmax_pay).
-template <bool DEF, bool FOLD, bool WIN>
+// PI: the ports-and-images form (option spread_ports_images; never with FOLD).  The static words are
+// k_static_pi's (SWPI_*: 13 bits of raw NodeAffinity, the ImageLocality score in bits 25-31); a pod's
+// NodePorts masks are the last uint4 of its record (an SPort behind the references: the header and
+// with it every other kernel's code stay as they were, and the masks ride the record's prefetch);
+// UsedPorts is a column of LDS (pused, one uint64 per slot) loaded and handed over with the rows.
+// The NodePorts verdict is in e.f before the PodTopologySpread / InterPodAffinity filters and before
+// every statistic of the filter pass, which count feasible nodes only (PreScore's filteredNodes).
+// The ImageLocality score travels above the Fit score in L.sfit (pi_fix: fit | il << 8).  AssumePod:
+// the winner's slot ORs port_add on lane 6 of the commit block, before the pod's closing barrier;
+// the column is read only by the next pod's filter pass.
+template <bool DEF, bool FOLD, bool WIN, bool PI = false>
 __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, const GPod* __restrict__ gpods,
                                                 const uint32_t* __restrict__ stat, const int32_t* __restrict__ res_rows,
                                                 int n_res, int k0, int k1, int32_t* chosen, PodMeta* meta,
@@ -1518,6 +1534,11 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
   SpreadHdr& H = *reinterpret_cast<SpreadHdr*>(smem);
   const SpreadShard L = spread_view(smem, cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD);
   const int nsc = c.n_scalar;
+  static_assert(!(FOLD && PI), "no statistics fold in the ports-and-images form");
+  uint64_t* const pused =
+      PI ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(smem) +
+                                       spread_lds_bytes(cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD))
+         : nullptr;
   // FOLD: pod j's static words in slot j % 3 (its early statistics pass reads pod k + 1's during
   // pod k) and its bins in area j & 1; otherwise slot j & 1 and one area
   auto st_slot = [](int j) { return FOLD ? j % 3 : j & 1; };
@@ -1531,7 +1552,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
   // (no HBM store on the exchange wave while the loop runs)
   unsigned long long* stl =
       stamps ? reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(smem) +
-                                                     spread_lds_bytes(cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD))
+                                                     spread_lds_bytes(cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD, PI))
              : nullptr;
   if (stl)
     for (int i = tid; i < 16 * nst; i += nt) stl[i] = 0;
@@ -1580,6 +1601,12 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
         const int64_t v = shd ? ld_ag(&hc.shadow[a * N + n]) : ld_ag(&c.requested[(size_t)(3 + i) * N + n]);
         L.sc[(size_t)(nsc + i) * cap + s] = v;
         h += handoff_mix((unsigned long long)v, a * N + n);
+      }
+      if constexpr (PI) {  // UsedPorts: the shadow column behind the scalar columns
+        const size_t a = 6 + (size_t)n_res + nsc;
+        const uint64_t pu = shd ? (uint64_t)ld_ag(&hc.shadow[a * N + n]) : ld_ag(&c.port_used[n]);
+        pused[s] = pu;
+        h += handoff_mix((unsigned long long)pu, a * N + n);
       }
     }
     for (int i = tid; i < n_res * own; i += nt) {
@@ -1865,6 +1892,8 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       for (int i = 0; i < G_PF; i++) H.wc[i][wave] = H.wb[i][wave] = 0;
     if (evaluated) {
       const SPod qd = q.dyn;  // in registers: the loop's LDS stores would make every field a reload
+      uint64_t qconflict = 0;  // PI: the pod's NodePorts conflict mask (the record's last uint4)
+      if constexpr (PI) qconflict = reinterpret_cast<const SPort*>(L.ring + (k % 3) * gq + gq - 1)->conflict;
       for (int s = tid; s < own; s += nt) {
         const uint32_t wd = sw[s];
         DynRow r;
@@ -1879,6 +1908,8 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
         r.pods = L.r32[s];
         r.allowed = L.r32[cap + s];
         SVal e = DEF ? dyn_eval_def(qd, wd, r) : dyn_eval(prof, qd, wd, r);
+        // NodePorts, the 13-bit NodeAffinity field, ImageLocality into e.fit (fit | il << 8)
+        if constexpr (PI) pi_fix<DEF>(prof, e, pused[s], qconflict);
         if (nsc && e.f == 0 && ((en >> KSS_F_NODE_RESOURCES_FIT) & 1u) && scalar_short(L.sc, nsc, cap, s, q.dyn, false, q.dyn))
           e.f = KSS_F_NODE_RESOURCES_FIT;
         if (e.f == 0 && ((en >> KSS_F_POD_TOPOLOGY_SPREAD) & 1u) && q.n_hard > 0 &&
@@ -2204,7 +2235,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
           // DefaultNormalizeScore(100, reverse=true) / (100, reverse=false); quotients <= 100
           nm[KSS_S_TAINT_TOLERATION] = max_tt == 0 ? 100 : 100 - small_div(100 * L.stt[s], max_tt, rtt);
           nm[KSS_S_NODE_AFFINITY] = max_na != 0 ? small_div(100 * L.sna[s], max_na, rna) : L.sna[s];
-          nm[KSS_S_NODE_RESOURCES_FIT] = L.sfit[s];
+          nm[KSS_S_NODE_RESOURCES_FIT] = PI ? (L.sfit[s] & 0xFF) : L.sfit[s];
           nm[KSS_S_VOLUME_BINDING] = 0;
           {  // PodTopologySpread.NormalizeScore
             int64_t raw = 0;
@@ -2228,7 +2259,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
             nm[KSS_S_INTER_POD_AFFINITY] = (int64_t)f;
           }
           nm[KSS_S_BALANCED_ALLOCATION] = L.sba[s];
-          nm[KSS_S_IMAGE_LOCALITY] = 0;
+          nm[KSS_S_IMAGE_LOCALITY] = PI ? (L.sfit[s] >> 8) : 0;  // final: ImageLocality has no NormalizeScore
 #pragma unroll
           for (int x = 0; x < KSS_NSCORE; x++)
             if ((prof.score_enabled >> x) & 1u) total += nm[x] * (int64_t)prof.weight[x];
@@ -2306,6 +2337,8 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       const SPod& pk = q.dyn;
       if (tid < 5) L.r64[(3 + tid) * cap + s] += (&pk.creq[0])[tid];
       if (tid == 5) L.r32[s] += 1;
+      if constexpr (PI)
+        if (tid == 6) pused[s] |= reinterpret_cast<const SPort*>(L.ring + (k % 3) * gq + gq - 1)->add;
       if (tid >= 8 && tid < 8 + nsc) L.sc[(size_t)(nsc + tid - 8) * cap + s] += pk.sc_req[tid - 8];
       if (tid == 32)
         for (int i = 0; i < q.n_cmt; i++)
@@ -2367,6 +2400,10 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       st_ag(&c.requested[(size_t)(3 + i) * N + n], v);
       if (hc.shadow) st_ag(&hc.shadow[(6 + (size_t)n_res + i) * N + n], (long long)v);
     }
+    if constexpr (PI) {
+      st_ag(&c.port_used[n], pused[s]);
+      if (hc.shadow) st_ag(&hc.shadow[(6 + (size_t)n_res + nsc) * N + n], (long long)pused[s]);
+    }
   }
   unsigned long long h = 0;
   if (hc.sum)
@@ -2379,6 +2416,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
            handoff_mix((unsigned long long)(uint32_t)L.r32[s], 5 * N + n);
       for (int i = 0; i < nsc; i++)
         h += handoff_mix((unsigned long long)L.sc[(size_t)(nsc + i) * cap + s], (6 + (size_t)n_res + i) * N + n);
+      if constexpr (PI) h += handoff_mix((unsigned long long)pused[s], (6 + (size_t)n_res + nsc) * N + n);
     }
   for (int i = tid; i < n_res * own; i += nt) {
     const int r = i / own, s = i - r * own, row = res_rows[r];

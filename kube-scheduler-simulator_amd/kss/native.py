@@ -79,6 +79,7 @@ SIGNATURES = [
     ("kss_buffer_map", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), C.c_int32, P(C.c_int32)]),
     ("kss_last_geometry", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_kernel", C.c_int, [C.c_void_p]),
+    ("kss_last_spread_lds", C.c_int, [C.c_void_p, P(C.c_int64)]),
     ("kss_last_xcd_local", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_shape_table", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_simple_exchange", C.c_int, [C.c_void_p, P(C.c_int32)]),
@@ -667,6 +668,13 @@ class Context:
         out = (C.c_int32 * 3)()
         check(lib().kss_last_geometry(self.h, out))
         return {"shards": out[0], "threads": out[1], "nodes_per_lane": out[2]}
+
+    def last_spread_lds(self) -> int:
+        """LDS bytes per workgroup of the last batch's k_spread launches (kss_last_spread_lds; 0:
+        another kernel)."""
+        v = C.c_int64(0)
+        check(lib().kss_last_spread_lds(self.h, C.byref(v)))
+        return v.value
 
     def last_xcd_local(self) -> Dict[str, int]:
         """{used, fallbacks} of the last run's XCD-local k_simple grid (kss_last_xcd_local)."""
