@@ -473,7 +473,12 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * k_spread's ports-and-images form instead of k_schedule -- on one part, with "fold" 0 and an empty
  * nominator, chunked launches and the window included -- provided every pod's preferred NodeAffinity
  * weights sum to at most 8191; batches without such pods are routed and launched as with 0;
- * kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
+ * kss_plan_podset follows it), "service_ports_images" (default 0, independent of the three
+ * above; 1: a staged list whose pods hold host ports or node-cached images is staged with records
+ * of the ports-and-images form, and the service grid evaluates it on its k_simple-shaped chain
+ * (kss_service_mode 1 / 2, kss_service_form 1) under that chain's other conditions, provided no
+ * pod has a volume program and every pod's preferred NodeAffinity weights sum to at most 8191;
+ * which kernel a staged batch runs on does not follow it; kss_plan_service follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -609,13 +614,22 @@ int kss_service_rollback(kss_ctx* ctx, int32_t pod_index, int32_t node);
  * record stores issued before the key exchange (out8[5..7], 0 otherwise). */
 int kss_service_stamps(kss_ctx* ctx, uint64_t* out8);
 /* Which evaluation the service grid runs (set when it starts): 1 the k_simple-shaped chain
- * (staged default-profile pods: no spread / inter-pod programs, host ports, node-cached images,
- * volumes or extended resources; below percentageOfNodesToScore 100 no PreFilterResult node
- * lists, the window running on the same chain) with the record stored from
+ * (staged default-profile pods: no spread / inter-pod programs, volumes or extended resources;
+ * below percentageOfNodesToScore 100 no PreFilterResult node lists, the window running on the
+ * same chain) with the record stored from
  * registers, 2 the same on an XCD-local grid (its exchanges in one XCD's L2), 0 the general
- * chain (schedule_pod + the record copy), -1 not started.  A non-empty nominator does not change
+ * chain (schedule_pod + the record copy), -1 not started.  A staged list in which some pod holds
+ * a host port or names a node-cached image runs the general chain, unless the option
+ * "service_ports_images" is 1: then it takes the k_simple-shaped chain in its ports-and-images
+ * form (kss_service_form), given the static-word table (it fits 4 GiB and "svc_no_static" is 0),
+ * every pod's preferred NodeAffinity weights summing to at most 8191 and LDS for one more word per
+ * node slot.  A non-empty nominator does not change
  * the mode: each chain has an instantiation that reads the table, launched while it holds entries. */
 int kss_service_mode(kss_ctx* ctx, int32_t* mode);
+/* The form of the running grid: out2[0] = 1 when it is an instantiation of the ports-and-images
+ * form (NodePorts decided in the chain on UsedPorts held in LDS, ImageLocality in the record), else
+ * 0; out2[1] = the LDS bytes per workgroup of its last launch (0 before the first). */
+int kss_service_form(kss_ctx* ctx, int32_t* out2);
 /* commit pod ps.pods[pod_index] to node (AssumePod); rollback undoes it (Unreserve/ForgetPod).
  * The deltas travel in the kernel's arguments (no upload). */
 int kss_commit(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, int32_t node);
@@ -943,10 +957,20 @@ int kss_abi_sizes(int32_t* out, int32_t n);
  * WITH spread / inter-pod programs follows the option "spread_ports_images" instead: 1 plans it on
  * k_spread (its ports-and-images form) under the same two conditions and with the option "fold" 0
  * (the 8191 limit has a reason of its own there, naming k_spread).  Sweeps, the split grid, the node
- * axis and the service grid refuse such pods whatever the options say.  The
+ * axis refuse such pods whatever the options say; the service grid follows an option of its own,
+ * "service_ports_images" (kss_plan_service), which changes nothing here.  The
  * option "table_images" changes nothing here: with or without the shape table the kernel is
  * k_simple. */
 int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3);
+/* Host only: the chain the service grid would pick for `ps` staged on `cl` under `prof` (NULL:
+ * the default profile), before geometry: out3[0] = 1 the k_simple-shaped chain, 0 the general
+ * chain; out3[1] = the first refusing pod (-1 none), out3[2] = the reason code (kss_plan_reason).
+ * Follows the process-wide option "service_ports_images" the way kss_plan_podset follows
+ * "simple_ports_images": with 0 a pod with host ports or node-cached images refuses, with 1 the
+ * list is planned on the ports-and-images form unless a pod has a volume program or preferred
+ * NodeAffinity weights above 8191 (reasons of their own, naming the service).  The start still
+ * checks LDS geometry, value bounds, the static-word table and the option "service_general". */
+int kss_plan_service(const kss_cluster* cl, const kss_podset* ps, const kss_profile* prof, int32_t* out3);
 /* The same with the profile the batch runs under (NULL: kss_plan_podset): a profile with
  * percentageOfNodesToScore below 100 on a cluster of 100+ nodes (the findNodesThatPassFilters
  * window) keeps k_simple only when no pod has a NodeAffinity PreFilterResult list, and rules out

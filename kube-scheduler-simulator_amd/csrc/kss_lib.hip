@@ -82,7 +82,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_N
 };
 struct OptDef {
   const char* name;
@@ -123,6 +123,7 @@ const OptDef kOptDefs[O_N] = {
     {"simple_ports_images", "KSS_SIMPLE_PORTS_IMAGES", 0},  // k_simple's ports-and-images form for NodePorts / ImageLocality pods
     {"table_images", "KSS_TABLE_IMAGES", 0},                // that form's batches without a host-port pod on the shape-table loop
     {"spread_ports_images", "KSS_SPREAD_PORTS_IMAGES", 0},  // k_spread's ports-and-images form (independent of simple_ports_images)
+    {"service_ports_images", "KSS_SERVICE_PORTS_IMAGES", 0},  // the service grid's k_simple-shaped chain for such pods (independent of the three above)
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -315,7 +316,10 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_schedule(const DevJob* __re
 // pinned ring starting at command `seq`.  NOM: the grid reads the nominator's table (job.nom);
 // instantiations of their own, launched only while the table is not empty, so the kernels of the
 // empty nominator keep their code and register allocation.
-template <bool GEN, bool SIMPLE, bool INL = false, bool NOM = false>
+// PI: the k_simple-shaped chain's ports-and-images form (option service_ports_images): two more
+// instantiations, <false, true, false, NOM, true>, launched only for a staged list that holds a
+// NodePorts / ImageLocality pod.
+template <bool GEN, bool SIMPLE, bool INL = false, bool NOM = false, bool PI = false>
 __global__ __launch_bounds__(KSS_MAX_THREADS) void k_service(const DevJob* __restrict__ jobs, kss_profile prof, int W,
                                                              int npt, int bins_cap, int cache_keys,
                                                              unsigned long long* gran, int* err, SvcBox* box,
@@ -324,7 +328,7 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_service(const DevJob* __res
                                                              int xcd) {
   extern __shared__ __attribute__((aligned(16))) long long smem[];
   const DevJob job = jobs[0];
-  service_loop<GEN, SIMPLE, INL, NOM>(job.c, job, prof, W, npt, bins_cap, cache_keys, gran, err, box, relay, seen, rec_host,
+  service_loop<GEN, SIMPLE, INL, NOM, PI>(job.c, job, prof, W, npt, bins_cap, cache_keys, gran, err, box, relay, seen, rec_host,
                                       seq, 0u, stamps, smem, xcd);
 }
 
@@ -1041,6 +1045,8 @@ struct kss_ctx {
     std::vector<DevNom> nom_host;
     DevJob job_host{};
     size_t shmem_nom = 0;  // LDS of a launch that reads the table (SIMPLE: + 8 bytes per node slot)
+    bool pi = false;       // the ports-and-images form (option service_ports_images): + 8 bytes per node slot in both
+    size_t shmem_last = 0;  // LDS of the last launch (kss_service_form)
   } svc;
   // split grid (kss_split_*): this context runs part split_part of split_n, split_wl shards
   // each; split_inbox is its exchange inbox (uncached device memory, zeroed once), split_peer
@@ -1341,14 +1347,17 @@ struct PiRecords {
   int na_pod = -1;
   std::vector<SPort> ports;
 };
+// svc (staging only): the option service_ports_images asks for that form as well -- the service
+// grid reads the staged records; which kernel a staged batch runs on still follows
+// simple_ports_images alone (run_single).
 bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr,
-                 PiRecords* pi = nullptr) {
+                 PiRecords* pi = nullptr, bool svc = false) {
   out.assign((size_t)std::max(ps->n_pods, 1), SPod{});
   if (n_shapes) *n_shapes = 0;
   bool form = false;
   if (pi) {
     *pi = PiRecords{};
-    if (opt(O_SIMPLE_PI))
+    if (opt(O_SIMPLE_PI) || (svc && opt(O_SERVICE_PI)))
       for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
     pi->form = form;
     if (form) pi->ports.assign((size_t)std::max(ps->n_pods, 1), SPort{});
@@ -1407,6 +1416,12 @@ enum {
   GP_SCALAR_SCORED,
   GP_PI_NA_WEIGHTS,
   GP_SPREAD_PI_NA_WEIGHTS,
+  GP_SVC_PROGRAMS,
+  GP_SVC_PORTS_IMAGES,
+  GP_SVC_VOLUMES,
+  GP_SVC_PI_NA_WEIGHTS,
+  GP_SVC_SCALAR,
+  GP_SVC_PCT_NAMES,
   GP_NCODES
 };
 const char* const kGpReason[GP_NCODES] = {
@@ -1431,6 +1446,14 @@ const char* const kGpReason[GP_NCODES] = {
     "ports-and-images form keeps 13 bits of raw NodeAffinity): k_schedule only",
     "preferred NodeAffinity weights above 8191 in a batch with programs and host ports or node-cached images "
     "(k_spread's ports-and-images form keeps 13 bits of raw NodeAffinity): k_schedule only",
+    "spread / inter-pod-affinity programs: the service's general chain",
+    "host ports (NodePorts) or node-cached images (ImageLocality) with the option service_ports_images 0: the "
+    "service's general chain",
+    "a volume program: the service's general chain (its k_simple-shaped chain takes no volumes, in either form)",
+    "preferred NodeAffinity weights above 8191 in a staged list with host ports or node-cached images (the service's "
+    "ports-and-images form keeps 13 bits of raw NodeAffinity): the service's general chain",
+    "the cluster has extended (scalar) resources: the service's general chain",
+    "percentageOfNodesToScore below 100 with a NodeAffinity PreFilterResult list: the service's general chain",
 };
 
 bool gfail(GpodNeeds& need, int code, int pod) {
@@ -3824,7 +3847,7 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
     ctx->staged_names |= ps->pods[i].names_len >= 0;
   }
   PiRecords pi;
-  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi);
+  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi, /*svc=*/true);
   ctx->spod_pi = ctx->spod_ok && pi.form;
   ctx->spod_ports = false;
   for (const SPort& q : pi.ports) ctx->spod_ports |= (q.conflict | q.add) != 0;
@@ -4374,7 +4397,10 @@ static int svc_launch(kss_ctx* ctx) {
   if (nomq)
     fn = v.gen ? (const void*)k_service<true, false, false, true>
                : (v.simple ? (const void*)k_service<false, true, false, true> : (const void*)k_service<false, false, false, true>);
+  // the ports-and-images form (svc_start_locked: v.pi implies v.simple): no INL x PI either
+  if (v.pi) fn = nomq ? (const void*)k_service<false, true, false, true, true> : (const void*)k_service<false, true, false, false, true>;
   const size_t shmem = nomq ? v.shmem_nom : v.shmem;
+  v.shmem_last = shmem;
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   const DevJob* jd = (const DevJob*)v.job.p;
   kss_profile pr = ctx->prof;
@@ -4421,7 +4447,9 @@ static int svc_start_locked(kss_ctx* ctx) {
   // no extended resources, exact f64 arithmetic, W <= 64 (its exchange:
   // one lane per shard), the node rows cached in LDS (checked below); KSS_SERVICE_GENERAL=1 keeps
   // the general chain, for comparison.  On an XCD-local grid when its shards fit one XCD's CUs.
-  const bool simple_pre = ctx->spod_ok && !ctx->spod_pi && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
+  // A staged list of the ports-and-images form (spod_pi) takes it only with the option
+  // service_ports_images on, the static-word table and room for the UsedPorts column (below).
+  const bool simple_pre = ctx->spod_ok && (!ctx->spod_pi || opt(O_SERVICE_PI)) && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
                           f64_exact(ctx->f64_cluster, ctx->f64_pods, ctx->staged_n) && !opt(O_SERVICE_GENERAL);
   const int xcd_cus = ctx->n_cu / XCD_GRID_MULT;
   // (off by default: the record's stores to host memory from one XCD were slower than the L2
@@ -4495,21 +4523,27 @@ static int svc_start_locked(kss_ctx* ctx) {
   job.cursor = (int32_t*)ctx->cursor_buf.p;
   // (a grid that reads the nominator keeps 8 more bytes of LDS per node slot: SvcNom::here)
   const size_t lds_cached = base + (cache_keys >= 0 ? node_cache_bytes(cap, cache_keys) : 0);
-  const bool nom_lds_ok = ctx->nom.empty() || lds_cached + 8 * (size_t)cap <= KSS_LDS_BUDGET;
-  v.simple = simple_pre && cache_keys >= 0 && g.W <= 64 && nom_lds_ok;
+  // (the ports-and-images form keeps 8 more per slot, the UsedPorts column, behind it; that form
+  // reads k_static_pi's words and has no inline evaluation of them: no table, no such grid)
+  const size_t pi_col = simple_pre && ctx->spod_pi ? 8 * (size_t)cap : 0;
+  const size_t stat_bytes = sizeof(uint32_t) * (size_t)std::max(ctx->staged_n, 1) * std::max<size_t>(N, 1);
+  const bool stat_ok = stat_bytes <= ((size_t)4 << 30) && !opt(O_SVC_NO_STATIC);
+  const bool nom_lds_ok = ctx->nom.empty() || lds_cached + 8 * (size_t)cap + pi_col <= KSS_LDS_BUDGET;
+  v.simple = simple_pre && cache_keys >= 0 && g.W <= 64 && nom_lds_ok &&
+             (!pi_col || (stat_ok && lds_cached + pi_col <= KSS_LDS_BUDGET));
+  v.pi = v.simple && pi_col != 0;
   v.xcd = v.simple && xcd_ok && g.W <= xcd_cus && g.W > 1;
   job.spods = v.simple ? (const SPod*)ctx->spod_buf.p : nullptr;
   // the static words of every staged pod (4 bytes per pod and node, at most 4 GiB): one load per
   // evaluation instead of the pod's requirement chains from HBM (KSS_SVC_NO_STATIC=1: inline)
-  const size_t stat_bytes = sizeof(uint32_t) * (size_t)std::max(ctx->staged_n, 1) * std::max<size_t>(N, 1);
-  const bool pre_static = v.simple && stat_bytes <= ((size_t)4 << 30) && !opt(O_SVC_NO_STATIC);
+  const bool pre_static = v.simple && stat_ok;
   if (pre_static && (rc = v.stat.ensure(stat_bytes))) return rc;
   job.stat = pre_static ? (uint32_t*)v.stat.p : nullptr;
   v.job_host = job;  // (nom / n_nom: svc_launch)
   HIP_TRY(hipMemcpyAsync(v.job.p, &v.job_host, sizeof(DevJob), hipMemcpyHostToDevice, v.stream));
   if (pre_static) {
     launch_static(v.stream, same_profile(ctx->prof, default_profile_c()), (const DevJob*)v.job.p, ctx->prof, 1, 0,
-                  ctx->staged_n, 0, (int)N, ctx->dc.n_keys);
+                  ctx->staged_n, 0, (int)N, ctx->dc.n_keys, 0, v.pi);
     HIP_TRY(hipGetLastError());
   }
   v.W = g.W;
@@ -4517,8 +4551,8 @@ static int svc_start_locked(kss_ctx* ctx) {
   v.npt = g.npt;
   v.bins_cap = bins_cap;
   v.cache_keys = cache_keys;
-  v.shmem = lds_cached;
-  v.shmem_nom = lds_cached + (v.simple ? 8 * (size_t)cap : 0);
+  v.shmem = lds_cached + (v.pi ? pi_col : 0);
+  v.shmem_nom = lds_cached + (v.simple ? 8 * (size_t)cap : 0) + (v.pi ? pi_col : 0);
   v.gen = std::max(need.bins_cap, 0) > 0 || need.general;
   ctx->last_geom[0] = g.W;
   ctx->last_geom[1] = g.threads;
@@ -4596,6 +4630,14 @@ int kss_service_mode(kss_ctx* ctx, int32_t* mode) {
   if (!ctx || !mode) return fail(KSS_E_INVAL, "bad arguments");
   std::lock_guard<std::mutex> lk(ctx->mu);
   *mode = ctx->svc.W > 0 ? (ctx->svc.simple ? (ctx->svc.xcd ? 2 : 1) : 0) : -1;
+  return 0;
+}
+
+int kss_service_form(kss_ctx* ctx, int32_t* out2) {
+  if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  out2[0] = ctx->svc.W > 0 && ctx->svc.pi ? 1 : 0;
+  out2[1] = ctx->svc.W > 0 ? (int32_t)ctx->svc.shmem_last : 0;
   return 0;
 }
 
@@ -5660,6 +5702,44 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
     out3[1] = ps->n_pods > 0 ? 0 : -1;
     out3[2] = GP_SCALAR_SCORED;
   }
+  return 0;
+}
+
+// The chain the service grid would pick for a staged list, before geometry (svc_start_locked's
+// simple_pre; the LDS budget, the value bounds and the static-word table are checked at the start).
+int kss_plan_service(const kss_cluster* cl, const kss_podset* ps, const kss_profile* prof, int32_t* out3) {
+  if (!cl || !ps || !out3) return fail(KSS_E_INVAL, "bad arguments");
+  int rc = check_cluster(cl);
+  if (rc) return rc;
+  if (prof && (rc = check_profile(prof))) return rc;
+  if ((rc = validate(cl, ps, ps->n_pods))) return rc;
+  out3[0] = 0;
+  out3[1] = -1;
+  out3[2] = GP_OK;
+  auto refuse = [&](int code, int pod) {
+    out3[1] = pod;
+    out3[2] = code;
+    return 0;
+  };
+  bool form = false;  // the ports-and-images form: some pod needs it and the option allows it
+  if (opt(O_SERVICE_PI))
+    for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
+  int names_pod = -1;
+  for (int i = 0; i < ps->n_pods; i++) {  // the first refusing pod, as build_spods walks them
+    const kss_pod& p = ps->pods[i];
+    if (p.n_hard | p.n_soft | p.ipa_len) return refuse(GP_SVC_PROGRAMS, i);
+    if (p.vol_len > 0) return refuse(GP_SVC_VOLUMES, i);
+    if (!form && pod_ports_images(p)) return refuse(GP_SVC_PORTS_IMAGES, i);
+    int64_t wsum = 0;
+    for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
+    if (wsum > 0xFFFFF) return refuse(GP_NA_WEIGHTS, i);
+    if (form && wsum > (int64_t)SWPI_NA_MAX) return refuse(GP_SVC_PI_NA_WEIGHTS, i);
+    if (names_pod < 0 && p.names_len >= 0) names_pod = i;
+  }
+  if (cl->n_scalar != 0) return refuse(GP_SVC_SCALAR, ps->n_pods > 0 ? 0 : -1);
+  const int pct = prof ? prof->pct_nodes_to_score : 100;
+  if (pct < 100 && names_pod >= 0) return refuse(GP_SVC_PCT_NAMES, names_pod);
+  out3[0] = 1;
   return 0;
 }
 

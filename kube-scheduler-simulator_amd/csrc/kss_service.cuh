@@ -16,7 +16,8 @@
 //               fences at system scope and stores done[w] = k + 1 (| SVC_DONE_OVF when a
 //               compact record value did not fit); a SIMPLE grid (staged default-profile
 //               pods) runs svc_simple_eval instead: the k_simple chain, record rows stored
-//               from registers
+//               from registers; its ports-and-images form (PI: option service_ports_images) also
+//               takes pods with host ports or node-cached images, UsedPorts held in LDS
 //     COMMIT / ROLLBACK   the owning shard applies AssumePod / ForgetPod (commit_pod); with a
 //               nominator (NOM grids) every shard also drops the committed pod's entry from its
 //               active mask (DeleteNominatedPodIfExists)
@@ -281,8 +282,9 @@ __device__ __forceinline__ unsigned svc_changed_rows(const uint8_t* a, const uin
 
 // ---------------------------------------------------------------------------
 // The k_simple-shaped evaluation (SIMPLE grids: staged default-profile pods -- no spread /
-// inter-pod programs, host ports, node-cached images, volumes or extended resources -- at
-// percentageOfNodesToScore 100).  Per node, from the shard's LDS node rows: the static part of
+// inter-pod programs, volumes or extended resources; host ports and node-cached images only in
+// the PI form below -- at percentageOfNodesToScore 100 or, without PreFilterResult lists, under
+// the window).  Per node, from the shard's LDS node rows: the static part of
 // the cycle (static_word: NodeUnschedulable, NodeName, TaintToleration, NodeAffinity and their raw
 // scores) and the state-dependent part (dyn_eval: NodeResourcesFit, the Fit and
 // BalancedAllocation scores) as k_simple computes them, one statistics exchange {feasible, max
@@ -692,10 +694,29 @@ __device__ __forceinline__ void svc_nom_load(SvcNom& sn, const DevJob& job, cons
   sn.here = here;
 }
 
-template <bool COMPACT, bool INL, bool NOM = false>
+// What ImageLocality adds to the selectHost key of a kept feasible node of a scored pod, given
+// sa.fit as the node pass packed it (Fit score | il << 8); leaves the Fit score in e.fit.  Its raw
+// score is its final score (no NormalizeScore), times its weight, in the key's total field.
+// pi_key_add's arithmetic (kss_simple.cuh), restated: instantiating that template here as well
+// changed the code of k_simple_pi's runtime-profile kernels.
+__device__ __forceinline__ long long svc_il_key(const kss_profile& prof, SVal& e, bool scored) {
+  const int il = e.fit >> 8;
+  e.fit &= 0xFF;
+  const bool on = scored && ((prof.score_enabled >> KSS_S_IMAGE_LOCALITY) & 1u);
+  return on ? (long long)((unsigned long long)(uint32_t)(il * prof.weight[KSS_S_IMAGE_LOCALITY]) << 32) : 0ll;
+}
+
+// PI (the ports-and-images form; option service_ports_images): the static words are
+// k_static_pi's (SWPI_*: 13 bits of raw NodeAffinity, the ImageLocality score in bits 25-31) and
+// pused[slot] is the node's UsedPorts word, the grid's only copy while it lives (service_loop).
+// NodePorts is decided on it before NodeResourcesFit and before the statistics, so a node that
+// fails both records NodePorts and leaves the feasible count; the ImageLocality score rides above
+// the Fit score in sa.fit to the second pass (pi_fix's packing) and enters raw, norm and, where the
+// score is enabled, the total and the selectHost key (it has no NormalizeScore).
+template <bool COMPACT, bool INL, bool NOM = false, bool PI = false>
 __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const kss_profile& prof, int pi, long long* smem,
                                 Shard& S, int bins_cap, int npt, unsigned want, uint8_t* host, PodMeta& meta, bool plain,
-                                unsigned long long* st3, const SvcNom* sn = nullptr) {
+                                unsigned long long* st3, const SvcNom* sn = nullptr, const uint64_t* pused = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const size_t N = (size_t)c.N;
   const SlotLayout L(N);
@@ -776,6 +797,9 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
   const int s0 = win ? (int)(((long long)S.cursor % c.N + c.N) % c.N) : 0;
   uint32_t wu[6] = {0, 0, 0, 0, 0, 0};  // this lane's {Fa, TTa, NAa, Fb, TTb, NAb}
   long long nf = 0, max_tt = 0, max_na = 0;
+  // PI: the pod's wanted ports (0 with the filter disabled: a pod without them never reads the column)
+  uint64_t pconf = 0;
+  if constexpr (PI) pconf = ((en >> KSS_F_NODE_PORTS) & 1u) ? p.port_conflict : 0ull;
   for (int k = 0; k < npt; k++) {
     const int n = S.lo + k * nt + tid;
     const int si = k * nt + tid;
@@ -786,8 +810,9 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     const NodeRow row = load_row(c, n);
     // the static word: precomputed for every staged pod at the grid's start (k_static into
     // job.stat, loaded above) or, without that table, evaluated here
-    const uint32_t w = !job.stat ? static_word(c, job.P, p, prof, n, row.flags, row.th, row.ts)
-                                 : (uint32_t)(hit ? sa.ipa[si] : sa.pts[si]);
+    // (a PI grid always has the table: the host starts none without it)
+    const uint32_t w = (!PI && !job.stat) ? static_word(c, job.P, p, prof, n, row.flags, row.th, row.ts)
+                                          : (uint32_t)(hit ? sa.ipa[si] : sa.pts[si]);
     DynRow dr;
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -800,6 +825,15 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     dr.pods = row.pods;
     dr.allowed = row.allowed;
     SVal e = dyn_eval(prof, q, w, dr);
+    int il = 0;
+    if constexpr (PI) {
+      // the word's PI layout: e.na still carries the ImageLocality score above the 13 NodeAffinity bits
+      il = e.na >> SWPI_NA_BITS;
+      e.na &= (int)SWPI_NA_MAX;
+      // NodePorts.Filter, ahead of NodeResourcesFit in the filter order: dyn_eval answers PASS or
+      // NodeResourcesFit only behind a clean static word
+      if (pconf && (e.f == KSS_F_PASS || e.f == KSS_F_NODE_RESOURCES_FIT) && (pused[si] & pconf)) e.f = KSS_F_NODE_PORTS;
+    }
     uint16_t detail = 0;
     bool first_failed = false, own_out = false;
     int f1 = KSS_F_PASS;
@@ -808,7 +842,9 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
       // local chain on the row with their requests and pod count added, in int64 (filter_local:
       // the f64 exactness bounds do not cover nominee sums).  Its failure is the node's verdict,
       // detail bits from the augmented row; otherwise the plain pass below decides.  A pod of this
-      // chain has no ports, volumes, spread or inter-pod entries, so filter_chain is filter_local.
+      // chain has no volumes, spread or inter-pod entries, so filter_chain is filter_local; on a PI
+      // grid its NodePorts test reads the node's word of the LDS column (c.port_used points there)
+      // with the nominees' ports added, so a node can fail NodePorts by a nominee alone.
       // A node outside the pod's NodeAffinity PreFilterResult list is never filtered, nominees or
       // not (schedule_pod's restrict_names): its slot stays KSS_F_NOT_EVALUATED ...
       const uint64_t here = sn->here[si] & elig;
@@ -840,7 +876,7 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     sa.fail[si] = e.f | ((int)detail << 8);
     sa.tt[si] = e.tt;
     sa.na[si] = e.na;
-    sa.fit[si] = e.fit;
+    sa.fit[si] = PI ? (e.fit | (il << 8)) : e.fit;
     sa.ba[si] = e.ba;
     if (e.f == KSS_F_PASS) {
       nf++;
@@ -913,8 +949,9 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     const int n = S.lo + k * nt + tid;
     const int si = k * nt + tid;
     if (n >= S.hi || (sa.fail[si] & 0xFF) != KSS_F_PASS || (n - s0 + c.N) % c.N >= pd) continue;
-    const SVal e{KSS_F_PASS, sa.tt[si], (int)sa.na[si], sa.fit[si], sa.ba[si]};
-    const long long key = simple_key(prof, e, scored, (int)max_tt, rtt, (int)max_na, rna, (uint32_t)(c.node_base + n));
+    SVal e{KSS_F_PASS, sa.tt[si], (int)sa.na[si], sa.fit[si], sa.ba[si]};
+    const long long ilk = PI ? svc_il_key(prof, e, scored) : 0ll;  // (e.fit back to the Fit score)
+    const long long key = simple_key(prof, e, scored, (int)max_tt, rtt, (int)max_na, rna, (uint32_t)(c.node_base + n)) + ilk;
     best = key > best ? key : best;
   }
   if (st3) st3[2] = wall_clock64();
@@ -938,11 +975,19 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
     const int f = fw & 0xFF;
     SVal e{f, sa.tt[si], (int)sa.na[si], sa.fit[si], sa.ba[si]};
     const bool pass = f == KSS_F_PASS && pos < pd;
+    int64_t r_il = 0, n_il = 0;
+    long long ilk = 0;
+    if constexpr (PI) {
+      const int il = e.fit >> 8;  // meaningful on a passing node only (the node pass packed it there)
+      ilk = svc_il_key(prof, e, pass && scored);
+      r_il = pass ? il : 0;
+      n_il = (pass && scored) ? il : 0;
+    }
     // the row values as scalars (a local array indexed in the store loop would go to scratch)
     const int64_t r_tt = pass ? e.tt : 0, r_na = pass ? e.na : 0, r_fit = pass ? e.fit : 0, r_ba = pass ? e.ba : 0;
     int64_t n_tt = 0, n_na = 0, n_fit = 0, n_pts = 0, n_ba = 0, total = 0;
     if (pass && scored) {
-      const long long key = simple_key(prof, e, scored, (int)max_tt, rtt, (int)max_na, rna, (uint32_t)(c.node_base + n));
+      const long long key = simple_key(prof, e, scored, (int)max_tt, rtt, (int)max_na, rna, (uint32_t)(c.node_base + n)) + ilk;
       n_tt = max_tt == 0 ? 100 : 100 - small_div(100 * e.tt, (int)max_tt, rtt);
       n_na = max_na != 0 ? small_div(100 * e.na, (int)max_na, rna) : e.na;
       n_fit = e.fit;
@@ -961,7 +1006,7 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
       svc_put<COMPACT>(host, o_raw, (size_t)KSS_S_POD_TOPOLOGY_SPREAD * N + n, es_raw, 0);
       svc_put<COMPACT>(host, o_raw, (size_t)KSS_S_INTER_POD_AFFINITY * N + n, es_raw, 0);
       svc_put<COMPACT>(host, o_raw, (size_t)KSS_S_BALANCED_ALLOCATION * N + n, es_raw, r_ba);
-      svc_put<COMPACT>(host, o_raw, (size_t)KSS_S_IMAGE_LOCALITY * N + n, es_raw, 0);
+      svc_put<COMPACT>(host, o_raw, (size_t)KSS_S_IMAGE_LOCALITY * N + n, es_raw, r_il);
     }
     if (w_norm) {
       svc_put<COMPACT>(host, o_norm, (size_t)KSS_S_TAINT_TOLERATION * N + n, es_norm, n_tt);
@@ -971,7 +1016,7 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
       svc_put<COMPACT>(host, o_norm, (size_t)KSS_S_POD_TOPOLOGY_SPREAD * N + n, es_norm, n_pts);
       svc_put<COMPACT>(host, o_norm, (size_t)KSS_S_INTER_POD_AFFINITY * N + n, es_norm, 0);
       svc_put<COMPACT>(host, o_norm, (size_t)KSS_S_BALANCED_ALLOCATION * N + n, es_norm, n_ba);
-      svc_put<COMPACT>(host, o_norm, (size_t)KSS_S_IMAGE_LOCALITY * N + n, es_norm, 0);
+      svc_put<COMPACT>(host, o_norm, (size_t)KSS_S_IMAGE_LOCALITY * N + n, es_norm, n_il);
     }
   }
   if (wd >= 0) S.cursor = wd;  // nextStartNodeIndex: the stopping node (every shard knows it)
@@ -996,7 +1041,7 @@ __device__ bool svc_simple_eval(const DevCluster& c, const DevJob& job, const ks
   return true;
 }
 
-template <bool GEN, bool SIMPLE, bool INL = false, bool NOM = false>
+template <bool GEN, bool SIMPLE, bool INL = false, bool NOM = false, bool PI = false>
 __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile& prof, int W, int npt, int bins_cap,
                              int cache_keys, unsigned long long* gran, int* err, SvcBox* box_flat,
                              unsigned long long* relay_flat, unsigned long long* seen_flat, uint8_t* rec_host,
@@ -1057,6 +1102,23 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
     svc_nom_load(sn, job, S, npt, reinterpret_cast<uint64_t*>(b + node_cache_bytes(cap, max(cache_keys, 0))));
   } else if constexpr (NOM) {
     nom_active = job.n_nom >= 64 ? ~0ull : ((1ull << job.n_nom) - 1ull);
+  }
+  // PI: UsedPorts as grid state.  One word per node slot behind the node cache (behind SvcNom::here
+  // on a NOM grid), loaded at every (re)launch and written back with the node cache when the grid
+  // leaves.  While the grid lives this column is the only copy read or written: c.port_used is
+  // pointed at it (slot k * nt + tid holds node lo + k * nt + tid, so c.port_used[n] is node n's
+  // slot for every node of this shard), which is where filter_local and commit_pod go for the
+  // shard's own nodes -- the only nodes this chain hands them.
+  uint64_t* pused = nullptr;
+  uint64_t* const port_hbm = c.port_used;
+  if constexpr (PI) {
+    static_assert(SIMPLE && !GEN, "the ports-and-images form is the k_simple-shaped chain's");
+    uint8_t* b = reinterpret_cast<uint8_t*>(xvec(smem) + NSCAL + bins_cap) + slot_arrays_bytes(cap);
+    pused = reinterpret_cast<uint64_t*>(b + node_cache_bytes(cap, max(cache_keys, 0)) + (NOM ? 8 * (size_t)cap : 0));
+    for (int i = threadIdx.x; i < cap; i += blockDim.x) pused[i] = S.lo + i < S.hi ? ld_ag(&port_hbm[S.lo + i]) : 0ull;
+    // (integer arithmetic: slot 0's address less lo words is no address inside the column)
+    c.port_used = reinterpret_cast<uint64_t*>(reinterpret_cast<uintptr_t>(pused) - 8 * (uintptr_t)S.lo);
+    __syncthreads();
   }
   if (SIMPLE) svc_prefetch(job, smem, S, bins_cap, npt, 0);
   int* cmd = shdr(smem).cmd;
@@ -1155,8 +1217,8 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
       if (node & 2) S.cursor = cursor_prev;  // the same scheduling cycle again
       cursor_prev = S.cursor;
       const bool ok =
-          compact ? svc_simple_eval<true, INL, NOM>(c, job, prof, pi, smem, S, bins_cap, npt, want, crec_host, m, plain, sp3, &sn)
-                  : svc_simple_eval<false, INL, NOM>(c, job, prof, pi, smem, S, bins_cap, npt, want, rec_host, m, plain, sp3, &sn);
+          compact ? svc_simple_eval<true, INL, NOM, PI>(c, job, prof, pi, smem, S, bins_cap, npt, want, crec_host, m, plain, sp3, &sn, pused)
+                  : svc_simple_eval<false, INL, NOM, PI>(c, job, prof, pi, smem, S, bins_cap, npt, want, rec_host, m, plain, sp3, &sn, pused);
       if (!ok) {
         if (threadIdx.x == 0) __hip_atomic_store(&box->err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         break;
@@ -1284,6 +1346,11 @@ __device__ void service_loop(DevCluster c, const DevJob& job, const kss_profile&
   if (c.nc64) {
     __syncthreads();
     cache_writeback(c, S.hi);
+  }
+  if constexpr (PI) {  // the column back to HBM: the next launch, a batch and kss_read_port_state see it
+    __syncthreads();
+    for (int i = threadIdx.x; i < cap; i += blockDim.x)
+      if (S.lo + i < S.hi) st_ag(&port_hbm[S.lo + i], pused[i]);
   }
   __threadfence_system();
   __syncthreads();

@@ -60,6 +60,7 @@ SIGNATURES = [
     ("kss_service_commit", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("kss_service_rollback", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("kss_service_mode", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("kss_service_form", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_service_stamps", C.c_int, [C.c_void_p, P(C.c_uint64)]),
     ("kss_commit", C.c_int, [C.c_void_p, P(abi.PodSet), C.c_int32, C.c_int32]),
     ("kss_rollback", C.c_int, [C.c_void_p, P(abi.PodSet), C.c_int32, C.c_int32]),
@@ -88,6 +89,8 @@ SIGNATURES = [
     ("kss_plan_podset", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.c_void_p]),
     ("kss_plan_podset_ex", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.POINTER(abi.Profile),
                                      C.c_void_p]),
+    ("kss_plan_service", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.POINTER(abi.Profile),
+                                  C.c_void_p]),
     ("kss_plan_reason", C.c_char_p, [C.c_int32]),
     ("kss_next_start_node_index", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_set_next_start_node_index", C.c_int, [C.c_void_p, C.c_int32]),
@@ -455,6 +458,13 @@ class Context:
         v = C.c_int32(-1)
         check(lib().kss_service_mode(self.h, C.byref(v)))
         return v.value
+
+    def service_form(self):
+        """(1 if the running grid is the ports-and-images form of the k_simple-shaped chain
+        (option service_ports_images) else 0, LDS bytes per workgroup of its last launch)."""
+        out = (C.c_int32 * 2)()
+        check(lib().kss_service_form(self.h, out))
+        return (int(out[0]), int(out[1]))
 
     def service_stop(self):
         check(lib().kss_service_stop(self.h))
@@ -829,3 +839,12 @@ def plan_podset(cluster: abi.Cluster, podset: abi.PodSet, profile: Optional[abi.
         check(lib().kss_plan_podset_ex(C.byref(cluster), C.byref(podset), C.byref(profile), out))
     kernel = {1: "k_simple", 2: "k_spread"}.get(out[0], "k_schedule")
     return {"kernel": kernel, "pod": out[1], "reason": lib().kss_plan_reason(out[2]).decode()}
+
+
+def plan_service(cluster: abi.Cluster, podset: abi.PodSet, profile: Optional[abi.Profile] = None) -> dict:
+    """Host-only: the chain the service grid would pick for the staged list, before geometry
+    (kss_plan_service): chain 1 the k_simple-shaped one, 0 the general one, with the first refusing
+    pod and the reason.  Follows the option service_ports_images."""
+    out = (C.c_int32 * 3)()
+    check(lib().kss_plan_service(C.byref(cluster), C.byref(podset), C.byref(profile) if profile is not None else None, out))
+    return {"chain": int(out[0]), "pod": int(out[1]), "reason": lib().kss_plan_reason(out[2]).decode()}
