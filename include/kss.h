@@ -631,7 +631,18 @@ int kss_service_mode(kss_ctx* ctx, int32_t* mode);
  * 0; out2[1] = the LDS bytes per workgroup of its last launch (0 before the first). */
 int kss_service_form(kss_ctx* ctx, int32_t* out2);
 /* commit pod ps.pods[pod_index] to node (AssumePod); rollback undoes it (Unreserve/ForgetPod).
- * The deltas travel in the kernel's arguments (no upload). */
+ * The deltas travel in the kernel's arguments (no upload).
+ * A pod with WaitForFirstConsumer claims: the rollback is RevertAssumedPodVolumes(podVolumes) --
+ * the PVs of the pod's own static bindings and the claims it provisioned go back to the loaded
+ * snapshot's pv_owner / claim_node, also where another committed pod sharing the claim had set
+ * them; nothing else changes.  The context does not keep podVolumes per pod: the rollback
+ * evaluates FindPodVolumes on the node again to find them.  LIMIT: that is exact when the commit
+ * being undone is the newest one still in place (a rollback right after its commit, or commits
+ * undone newest first).  Rolling a pod back after later pods were committed (an upstream binding
+ * cycle failing late) may find other picks than the commit made and restore those instead;
+ * a caller that rolls back out of order keeps the assume cache itself and loads the cluster again
+ * with its pv_owner / claim_node (kss_read_binding_state shows what the context holds).
+ * kss_service_rollback has the same semantics and the same limit. */
 int kss_commit(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, int32_t node);
 int kss_rollback(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, int32_t node);
 

@@ -497,8 +497,17 @@ __device__ __forceinline__ int vb_eval(const DevCluster& c, const kss_req* reqs,
 
 // Reserve's AssumePodVolumes (sign 1) on node `local`: the static bindings' PVs become the claims'
 // (pv_owner), the provisioned claims select the node (claim_node); Unreserve's
-// RevertAssumedPodVolumes (sign -1): the claims' PVs and the claims back to the snapshot's values.
-// Every shard of a grid runs it with the same result (the columns are global, not per node).
+// RevertAssumedPodVolumes (sign -1): the PVs of this pod's own static bindings and the claims it
+// provisioned back to the snapshot's values -- also where another assumed pod sharing the claim
+// had set them -- and nothing else (not every PV of the pod's claims: a PV another pod assumed
+// for a claim this pod provisioned elsewhere stays that pod's).  The pod's podVolumes are not
+// kept: FindPodVolumes on `local` over the current state finds them again -- a static binding's
+// PV is the one assumed for the claim, a provisioned claim is selected for `local` -- which is
+// exact while the commit undone is the newest live one (a rollback right after the commit, or
+// commits undone newest first); include/kss.h kss_rollback states the limit.
+// Every shard of a grid runs it with the same result (the columns are global, not per node): a
+// shard that reads another's restored values picks only free PVs (already the snapshot's) or the
+// same ones, and a claim whose selected node went back holds the snapshot's value already.
 template <class Lab>
 __device__ __forceinline__ void wffc_commit(const DevCluster& c, const kss_req* reqs, const kss_term* terms,
                                             const int32_t* ints, const kss_vol* vols, const kss_pod& p, int local,
@@ -513,27 +522,15 @@ __device__ __forceinline__ void wffc_commit(const DevCluster& c, const kss_req* 
   bool any = false;
   for (int e = e0; e < e1; e++) any |= vols[e].kind == KSS_VOL_BIND_WFFC;
   if (!any) return;
-  if (sign > 0) {
-    int pick[KSS_MAX_WFFC] = {-1, -1, -1, -1};
-    vb_eval(c, reqs, terms, ints, vols, e0, e1, local, lab, pick);
-    int wi = 0;
-    for (int e = e0; e < e1; e++) {
-      const kss_vol& v = vols[e];
-      if (v.kind != KSS_VOL_BIND_WFFC) continue;
-      if (wi < KSS_MAX_WFFC && pick[wi] >= 0) c.pv_owner[pick[wi]] = v.key + 1;
-      else c.claim_node[v.key] = local;
-      wi++;
-    }
-  } else {
-    for (int e = e0; e < e1; e++) {
-      const kss_vol& v = vols[e];
-      if (v.kind != KSS_VOL_BIND_WFFC) continue;
-      for (int i = 0; i < v.b; i++) {
-        const int pv = ints[v.a + 3 * i];
-        if (c.pv_owner[pv] == v.key + 1) c.pv_owner[pv] = c.pv_owner0[pv];
-      }
-      c.claim_node[v.key] = c.claim_node0[v.key];
-    }
+  int pick[KSS_MAX_WFFC] = {-1, -1, -1, -1};
+  vb_eval(c, reqs, terms, ints, vols, e0, e1, local, lab, pick);
+  int wi = 0;
+  for (int e = e0; e < e1; e++) {
+    const kss_vol& v = vols[e];
+    if (v.kind != KSS_VOL_BIND_WFFC) continue;
+    if (wi < KSS_MAX_WFFC && pick[wi] >= 0) c.pv_owner[pick[wi]] = sign > 0 ? v.key + 1 : c.pv_owner0[pick[wi]];
+    else c.claim_node[v.key] = sign > 0 ? local : c.claim_node0[v.key];
+    wi++;
   }
 }
 

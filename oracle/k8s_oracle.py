@@ -704,16 +704,15 @@ class Oracle:
         NodeInfo.AddPod, then SchedulingQueue.DeleteNominatedPodIfExists (schedule_one.go assume)."""
         if _spec(pod).get("volumes"):
             _, claims = self.storage.binding_prefilter(pod)
-            self.storage.assume(claims, self.infos[i].node, NodeSelectorTerms)
+            self.storage.assume(claims, self.infos[i].node, NodeSelectorTerms, pod_key=self._key(pod))
         self.infos[i].add_pod(pod)
         self.clear_nomination(pod)
 
     def forget(self, pod, i: int):
-        """Unreserve: VolumeBinding.Unreserve (RevertAssumedPodVolumes) and Cache.ForgetPod ->
-        NodeInfo.RemovePod."""
+        """Unreserve: VolumeBinding.Unreserve (RevertAssumedPodVolumes of the podVolumes this pod's
+        Reserve kept) and Cache.ForgetPod -> NodeInfo.RemovePod."""
         if _spec(pod).get("volumes"):
-            _, claims = self.storage.binding_prefilter(pod)
-            self.storage.revert(claims)
+            self.storage.revert(pod_key=self._key(pod))
         self.infos[i].remove_pod(pod)
 
     def filter_with_nominated(self, pod, i: int, ni: "NodeInfo", pts_st, ipa_st, vb_claims=None):

@@ -159,6 +159,7 @@ class Storage:
             if sel is not None:
                 self.selected0[key] = sel
         self.selected = dict(self.selected0)
+        self.pod_volumes = {}  # pod key -> (static bindings [(claim key, PV name)], provisioned claims' keys)
 
     # ------------------------------------------------------------ helpers
     @staticmethod
@@ -372,8 +373,17 @@ class Storage:
         if not terms:
             return True
         lb = _meta(node).get("labels") or {}
-        return any(all(e.get("key") in lb and lb[e.get("key")] in (e.get("values") or [])
-                       for e in t.get("matchLabelExpressions") or []) for t in terms)
+        for t in terms:  # MatchTopologySelectorTerms: the terms are ORed
+            exprs = t.get("matchLabelExpressions") or []
+            if not exprs:
+                continue  # "nil or empty term selects no objects"
+            # topologySelectorRequirementsAsSelector: an In requirement without values does not
+            # build (labels.NewRequirement's error), which fails the term
+            if any(not (e.get("values") or []) for e in exprs):
+                continue
+            if all(e.get("key") in lb and lb[e.get("key")] in e["values"] for e in exprs):
+                return True
+        return False
 
     def find_pod_volumes(self, claims, node, node_selector_terms):
         """binder.go FindPodVolumes: (reasons, static bindings [(pvc, pv name)], claims to provision)."""
@@ -429,9 +439,11 @@ class Storage:
         reasons, _, _ = self.find_pod_volumes(claims, node, node_selector_terms)
         return ", ".join(reasons) if reasons else None
 
-    def assume(self, claims, node, node_selector_terms):
+    def assume(self, claims, node, node_selector_terms, pod_key=None):
         """Reserve -> AssumePodVolumes on the chosen node: the static bindings' PVs get the
-        claim as claimRef, the provisioned claims the node as selected-node."""
+        claim as claimRef, the provisioned claims the node as selected-node.  The pod's podVolumes
+        (StaticBindings' PV names, DynamicProvisions' claim keys) stay in its cycle state until
+        Unreserve: kept here by pod_key."""
         if claims is None or not claims.delayed:
             return
         _, bindings, provision = self.find_pod_volumes(claims, node, node_selector_terms)
@@ -440,20 +452,21 @@ class Storage:
             self.pv_ref[pv] = (ns, name, _meta(pvc).get("uid") or "")
         for pvc in provision:
             self.selected[self._claim_key(pvc)] = _meta(node).get("name")
+        self.pod_volumes[pod_key] = ([(self._claim_key(pvc), pv) for pvc, pv in bindings],
+                                     [self._claim_key(pvc) for pvc in provision])
 
-    def revert(self, claims):
-        """Unreserve -> RevertAssumedPodVolumes: the claims' PVs and the claims back to the
-        informer's (snapshot) objects."""
-        if claims is None:
-            return
-        for pvc in claims.delayed:
-            key = self._claim_key(pvc)
-            for pv, ref in list(self.pv_ref.items()):
-                if (ref[0], ref[1]) == key and self.pv_ref0.get(pv) != ref:
-                    if pv in self.pv_ref0:
-                        self.pv_ref[pv] = self.pv_ref0[pv]
-                    else:
-                        del self.pv_ref[pv]
+    def revert(self, pod_key=None):
+        """Unreserve -> RevertAssumedPodVolumes(podVolumes) (v1.26 binder.go): pvCache.Restore of
+        the PVs in this pod's own StaticBindings and pvcCache.Restore of the claims in its own
+        DynamicProvisions, back to the informer's (snapshot) objects -- also where another assumed
+        pod sharing the claim had set the same PV or claim; nothing else changes."""
+        bindings, provision = self.pod_volumes.pop(pod_key, ((), ()))
+        for _, pv in bindings:
+            if pv in self.pv_ref0:
+                self.pv_ref[pv] = self.pv_ref0[pv]
+            else:
+                self.pv_ref.pop(pv, None)
+        for key in provision:
             if key in self.selected0:
                 self.selected[key] = self.selected0[key]
             else:

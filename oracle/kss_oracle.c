@@ -83,6 +83,8 @@ typedef struct {
   int32_t* vol_attached;
   int32_t* pv_owner;   /* the binder's assume cache (kss_cluster pv_owner / claim_node) */
   int32_t* claim_node;
+  const int32_t* pv_owner0; /* the snapshot's (the informer's objects, what a Restore goes back to) */
+  const int32_t* claim_node0;
   int32_t cursor; /* the scheduler's nextStartNodeIndex (schedule_one.go findNodesThatPassFilters) */
   /* the scheduling queue's nominator (PodNominator): pods of ps nominated to a node by an earlier
      preemption; a nomination leaves when its pod is assumed (DeleteNominatedPodIfExists) */
@@ -90,6 +92,9 @@ typedef struct {
   const int32_t* nom_pod;  /* [n_nom] index in ps */
   const int32_t* nom_node; /* [n_nom] local node */
   uint8_t* nom_active;     /* [n_nom] */
+  /* the podVolumes each assumed pod keeps in its cycle state from Reserve to Unreserve (NULL: not
+     kept): per pod and BIND_WFFC entry the static binding's PV, -1 a provisioned claim, -2 nothing */
+  int32_t* picks; /* [n_pods][KSS_MAX_WFFC] */
 } ostate;
 
 static int ostate_init(ostate* s, const kss_cluster* cl) {
@@ -99,6 +104,9 @@ static int ostate_init(ostate* s, const kss_cluster* cl) {
   s->n_nom = 0;
   s->nom_pod = s->nom_node = NULL;
   s->nom_active = NULL;
+  s->picks = NULL;
+  s->pv_owner0 = cl->pv_owner;
+  s->claim_node0 = cl->claim_node;
   s->requested = (int64_t*)malloc(sizeof(int64_t) * KSS_NRES * (N ? N : 1));
   s->nonzero = (int64_t*)malloc(sizeof(int64_t) * 2 * (N ? N : 1));
   s->pod_count = (int32_t*)malloc(sizeof(int32_t) * (N ? N : 1));
@@ -147,6 +155,7 @@ static void ostate_free(ostate* s) {
   free(s->pv_owner);
   free(s->claim_node);
   free(s->nom_active);
+  free(s->picks);
 }
 
 #define LV(cl, key, n) ((cl)->label_value[(size_t)(key) * (size_t)(cl)->n_nodes + (size_t)(n)])
@@ -1295,6 +1304,50 @@ done:
   return rc;
 }
 
+/* Reserve's AssumePodVolumes on node_local: the delayed claims' static bindings (pv_owner) and
+   provisioning on this node (claim_node); the podVolumes are kept for the pod's Unreserve. */
+static void assume_volumes(ostate* s, const kss_podset* ps, int pi, int node_local) {
+  const kss_pod* p = &ps->pods[pi];
+  int e0 = -1, e1 = -1;
+  for (int e = 0; e < p->vol_len; e++)
+    if (is_vb(ps->vols[p->vol_off + e].kind)) {
+      if (e0 < 0) e0 = p->vol_off + e;
+      e1 = p->vol_off + e + 1;
+    }
+  if (s->picks)
+    for (int k = 0; k < KSS_MAX_WFFC; k++) s->picks[(size_t)pi * KSS_MAX_WFFC + k] = -2;
+  if (e0 >= 0) {
+    int pick[KSS_MAX_WFFC] = {-1, -1, -1, -1}, wi = 0;
+    find_pod_volumes(&s->c, ps, e0, e1, node_local, pick);
+    for (int e = e0; e < e1; e++) {
+      const kss_vol* v = &ps->vols[e];
+      if (v->kind != KSS_VOL_BIND_WFFC) continue;
+      if (pick[wi] >= 0) s->pv_owner[pick[wi]] = v->key + 1;
+      else s->claim_node[v->key] = node_local;
+      if (s->picks) s->picks[(size_t)pi * KSS_MAX_WFFC + wi] = pick[wi];
+      wi++;
+    }
+  }
+}
+
+/* Unreserve's RevertAssumedPodVolumes(podVolumes) (v1.26 binder.go): pvCache.Restore of the PVs in
+   this pod's own StaticBindings, pvcCache.Restore of the claims in its own DynamicProvisions, each
+   back to the informer's (the snapshot's) object -- whoever else assumed them; nothing else moves. */
+static void revert_volumes(ostate* s, const kss_podset* ps, int pi) {
+  const kss_pod* p = &ps->pods[pi];
+  int wi = 0;
+  if (!s->picks) return;
+  for (int e = 0; e < p->vol_len; e++) {
+    const kss_vol* v = &ps->vols[p->vol_off + e];
+    if (v->kind != KSS_VOL_BIND_WFFC) continue;
+    int32_t* pk = &s->picks[(size_t)pi * KSS_MAX_WFFC + wi];
+    if (*pk >= 0) s->pv_owner[*pk] = s->pv_owner0[*pk];
+    else if (*pk == -1) s->claim_node[v->key] = s->claim_node0[v->key];
+    *pk = -2;
+    wi++;
+  }
+}
+
 /* Cache.AssumePod -> NodeInfo.AddPod (framework/types.go calculateResource) */
 static void commit(ostate* s, const kss_podset* ps, int pi, int node_local) {
   const kss_pod* p = &ps->pods[pi];
@@ -1320,24 +1373,33 @@ static void commit(ostate* s, const kss_podset* ps, int pi, int node_local) {
       s->vol_attached[(size_t)v->key * N + node_local] += v->count;
     }
   }
-  /* Reserve's AssumePodVolumes: the delayed claims' static bindings and provisioning on this node */
-  int e0 = -1, e1 = -1;
-  for (int e = 0; e < p->vol_len; e++)
-    if (is_vb(ps->vols[p->vol_off + e].kind)) {
-      if (e0 < 0) e0 = p->vol_off + e;
-      e1 = p->vol_off + e + 1;
-    }
-  if (e0 >= 0) {
-    int pick[KSS_MAX_WFFC] = {-1, -1, -1, -1}, wi = 0;
-    find_pod_volumes(&s->c, ps, e0, e1, node_local, pick);
-    for (int e = e0; e < e1; e++) {
-      const kss_vol* v = &ps->vols[e];
-      if (v->kind != KSS_VOL_BIND_WFFC) continue;
-      if (pick[wi] >= 0) s->pv_owner[pick[wi]] = v->key + 1;
-      else s->claim_node[v->key] = node_local;
-      wi++;
+  assume_volumes(s, ps, pi, node_local);
+}
+
+/* Cache.ForgetPod -> NodeInfo.RemovePod of a pod commit() put on node_local, and Unreserve's
+   RevertAssumedPodVolumes.  The nominator is left alone: a forgotten pod is not nominated again. */
+static void rollback(ostate* s, const kss_podset* ps, int pi, int node_local) {
+  const kss_pod* p = &ps->pods[pi];
+  size_t N = (size_t)s->c.n_nodes;
+  for (int r = 0; r < KSS_NRES; r++) s->requested[(size_t)r * N + node_local] -= p->commit_req[r];
+  s->nonzero[node_local] -= p->commit_nz[0];
+  s->nonzero[N + node_local] -= p->commit_nz[1];
+  s->pod_count[node_local] -= 1;
+  if (p->cls >= 0) s->class_count[(size_t)p->cls * N + node_local] -= 1;
+  for (int i = 0; i < p->own_terms_len; i++) s->term_count[(size_t)ps->ints[p->own_terms_off + i] * N + node_local] -= 1;
+  s->port_used[node_local] &= ~p->port_add; /* NodeInfo.RemovePod updateUsedPorts (no two pods of a node share a port) */
+  for (int e = 0; e < p->vol_len; e++) {
+    const kss_vol* v = &ps->vols[p->vol_off + e];
+    if (v->kind == KSS_VOL_OWN) {
+      int key = s->c.vol_row_key[v->row];
+      int32_t* cnt = &s->vol_count[(size_t)v->row * N + node_local];
+      *cnt -= 1;
+      if (key >= 0 && *cnt == 0) s->vol_attached[(size_t)key * N + node_local] -= 1;
+    } else if (v->kind == KSS_VOL_OWN_PRIVATE) {
+      s->vol_attached[(size_t)v->key * N + node_local] -= v->count;
     }
   }
+  revert_volumes(s, ps, pi);
 }
 
 /* ---------------------------------------------------------------------------
@@ -1415,9 +1477,12 @@ int kss_oracle_schedule_n(const kss_profile* prof, const kss_cluster* cl, const 
                                nom_pod, nom_node, n_nom, nom_left, NULL, NULL);
 }
 
-/* kss_oracle_schedule_w where pods with skip_commit[i] != 0 are evaluated but not assumed: the
-   per-pod API's commit followed by a rollback of the same pod (Reserve then Unreserve leave the
-   node state as it was; tests/test_gpu_service.py replays a service sequence with it). */
+/* kss_oracle_schedule_w where pods with skip_commit[i] != 0 are evaluated and their commit rolled
+   back at once: the per-pod API's commit followed by a rollback of the same pod.  Reserve then
+   Unreserve leave the node columns as they were, and the pod stays nominated; the assume cache is
+   left as AssumePodVolumes then RevertAssumedPodVolumes leave it, which is the snapshot's value for
+   every PV and claim in the pod's podVolumes -- not a no-op when another assumed pod shares a claim
+   (tests/test_gpu_service.py replays a service sequence with it). */
 int kss_oracle_schedule_wm(const kss_profile* prof, const kss_cluster* cl, const kss_podset* ps, int n,
                            int32_t* chosen, kss_pod_result* results, int threads, int64_t* out_requested,
                            int64_t* out_nonzero, int32_t* out_pod_count, int32_t* out_class_count,
@@ -1438,6 +1503,22 @@ int kss_oracle_schedule_w(const kss_profile* prof, const kss_cluster* cl, const 
                                 cursor, nom_pod, nom_node, n_nom, nom_left, out_pv_owner, out_claim_node, NULL);
 }
 
+/* kss_oracle_schedule_wm over a program of n steps: ops[k] >= 0 schedules pod ops[k] (assumed unless
+   skip_commit[ops[k]]); ops[k] < 0 is the Unreserve of pod -1 - ops[k] on the node its commit chose
+   (rollback(): ForgetPod and RevertAssumedPodVolumes of that pod's own podVolumes; chosen[k] is that
+   node, -1 when the pod is not assumed).  ops NULL: pods [0, n) in order.  chosen and results go by
+   step.  trace_* (optional): the volume columns and the assume cache after every step
+   ([n][n_vol_rows][N], [n][n_vol_keys][N], [n][n_pvs], [n][n_wclaims]). */
+int kss_oracle_schedule_wr(const kss_profile* prof, const kss_cluster* cl, const kss_podset* ps, int n,
+                           int32_t* chosen, kss_pod_result* results, int threads, int64_t* out_requested,
+                           int64_t* out_nonzero, int32_t* out_pod_count, int32_t* out_class_count,
+                           int32_t* out_term_count, uint64_t* out_port_used, int32_t* out_vol_count,
+                           int32_t* out_vol_attached, int32_t* cursor, const int32_t* nom_pod,
+                           const int32_t* nom_node, int32_t n_nom, uint8_t* nom_left, int32_t* out_pv_owner,
+                           int32_t* out_claim_node, const uint8_t* skip_commit, const int32_t* ops,
+                           int32_t* trace_vol_count, int32_t* trace_vol_attached, int32_t* trace_pv_owner,
+                           int32_t* trace_claim_node);
+
 int kss_oracle_schedule_wm(const kss_profile* prof, const kss_cluster* cl, const kss_podset* ps, int n,
                            int32_t* chosen, kss_pod_result* results, int threads, int64_t* out_requested,
                            int64_t* out_nonzero, int32_t* out_pod_count, int32_t* out_class_count,
@@ -1445,6 +1526,21 @@ int kss_oracle_schedule_wm(const kss_profile* prof, const kss_cluster* cl, const
                            int32_t* out_vol_attached, int32_t* cursor, const int32_t* nom_pod,
                            const int32_t* nom_node, int32_t n_nom, uint8_t* nom_left, int32_t* out_pv_owner,
                            int32_t* out_claim_node, const uint8_t* skip_commit) {
+  return kss_oracle_schedule_wr(prof, cl, ps, n, chosen, results, threads, out_requested, out_nonzero, out_pod_count,
+                                out_class_count, out_term_count, out_port_used, out_vol_count, out_vol_attached,
+                                cursor, nom_pod, nom_node, n_nom, nom_left, out_pv_owner, out_claim_node, skip_commit,
+                                NULL, NULL, NULL, NULL, NULL);
+}
+
+int kss_oracle_schedule_wr(const kss_profile* prof, const kss_cluster* cl, const kss_podset* ps, int n,
+                           int32_t* chosen, kss_pod_result* results, int threads, int64_t* out_requested,
+                           int64_t* out_nonzero, int32_t* out_pod_count, int32_t* out_class_count,
+                           int32_t* out_term_count, uint64_t* out_port_used, int32_t* out_vol_count,
+                           int32_t* out_vol_attached, int32_t* cursor, const int32_t* nom_pod,
+                           const int32_t* nom_node, int32_t n_nom, uint8_t* nom_left, int32_t* out_pv_owner,
+                           int32_t* out_claim_node, const uint8_t* skip_commit, const int32_t* ops,
+                           int32_t* trace_vol_count, int32_t* trace_vol_attached, int32_t* trace_pv_owner,
+                           int32_t* trace_claim_node) {
   ostate s;
   if (ostate_init(&s, cl)) return KSS_E_NOMEM;
   if (cursor) s.cursor = *cursor;
@@ -1462,16 +1558,63 @@ int kss_oracle_schedule_wm(const kss_profile* prof, const kss_cluster* cl, const
   }
   int th = threads > 0 ? threads : 1;
   int rc = 0;
-  for (int i = 0; i < n; i++) {
-    kss_pod_result tmp;
-    memset(&tmp, 0, sizeof(tmp));
-    kss_pod_result* out = results ? &results[i] : &tmp;
-    rc = schedule_one(prof, &s, ps, i, out, th);
-    if (rc) break;
-    chosen[i] = out->chosen;
-    if (out->chosen >= 0 && !(skip_commit && skip_commit[i])) commit(&s, ps, i, out->chosen - cl->node_base);
-  }
   size_t N = (size_t)cl->n_nodes;
+  int np = ps->n_pods > 0 ? ps->n_pods : 1;
+  s.picks = (int32_t*)malloc(sizeof(int32_t) * (size_t)np * KSS_MAX_WFFC);
+  int32_t* assumed_on = (int32_t*)malloc(sizeof(int32_t) * (size_t)np); /* local node of the pod's live commit, -1 */
+  if (!s.picks || !assumed_on) rc = KSS_E_NOMEM;
+  for (int i = 0; !rc && i < np; i++) {
+    assumed_on[i] = -1;
+    for (int k = 0; k < KSS_MAX_WFFC; k++) s.picks[(size_t)i * KSS_MAX_WFFC + k] = -2;
+  }
+  for (int k = 0; !rc && k < n; k++) {
+    int op = ops ? ops[k] : k;
+    int i = op >= 0 ? op : -1 - op;
+    if (i >= ps->n_pods) {
+      rc = KSS_E_INVAL;
+      break;
+    }
+    if (op < 0) { /* Unreserve */
+      chosen[k] = -1;
+      if (assumed_on[i] >= 0) {
+        chosen[k] = assumed_on[i] + cl->node_base;
+        rollback(&s, ps, i, assumed_on[i]);
+        assumed_on[i] = -1;
+      }
+    } else {
+      kss_pod_result tmp;
+      memset(&tmp, 0, sizeof(tmp));
+      kss_pod_result* out = results ? &results[k] : &tmp;
+      rc = schedule_one(prof, &s, ps, i, out, th);
+      if (rc) break;
+      chosen[k] = out->chosen;
+      if (out->chosen >= 0 && assumed_on[i] < 0) {
+        int local = out->chosen - cl->node_base;
+        if (skip_commit && skip_commit[i]) {
+          /* a commit the caller rolled back at once: the node columns as they were and the pod's
+             nomination kept (it never left the queue) -- but not a no-op on the assume cache:
+             Reserve's AssumePodVolumes followed by Unreserve's RevertAssumedPodVolumes restores the
+             PVs and claims of this pod's podVolumes to the snapshot's, also where another assumed
+             pod that shares the claim had set them */
+          assume_volumes(&s, ps, i, local);
+          revert_volumes(&s, ps, i);
+        } else {
+          commit(&s, ps, i, local);
+          assumed_on[i] = local;
+        }
+      }
+    }
+    if (trace_vol_count && cl->n_vol_rows)
+      memcpy(trace_vol_count + (size_t)k * cl->n_vol_rows * N, s.vol_count, sizeof(int32_t) * (size_t)cl->n_vol_rows * N);
+    if (trace_vol_attached && cl->n_vol_keys)
+      memcpy(trace_vol_attached + (size_t)k * cl->n_vol_keys * N, s.vol_attached,
+             sizeof(int32_t) * (size_t)cl->n_vol_keys * N);
+    if (trace_pv_owner && cl->n_pvs)
+      memcpy(trace_pv_owner + (size_t)k * cl->n_pvs, s.pv_owner, sizeof(int32_t) * (size_t)cl->n_pvs);
+    if (trace_claim_node && cl->n_wclaims)
+      memcpy(trace_claim_node + (size_t)k * cl->n_wclaims, s.claim_node, sizeof(int32_t) * (size_t)cl->n_wclaims);
+  }
+  free(assumed_on);
   if (out_requested) memcpy(out_requested, s.requested, sizeof(int64_t) * KSS_NRES * N);
   if (out_nonzero) memcpy(out_nonzero, s.nonzero, sizeof(int64_t) * 2 * N);
   if (out_pod_count) memcpy(out_pod_count, s.pod_count, sizeof(int32_t) * N);

@@ -34,6 +34,8 @@ def lib():
         _lib.kss_oracle_schedule_w.restype = C.c_int
         _lib.kss_oracle_schedule_wm.argtypes = _lib.kss_oracle_schedule_w.argtypes + [P(C.c_uint8)]
         _lib.kss_oracle_schedule_wm.restype = C.c_int
+        _lib.kss_oracle_schedule_wr.argtypes = _lib.kss_oracle_schedule_wm.argtypes + [P(C.c_int32)] * 5
+        _lib.kss_oracle_schedule_wr.restype = C.c_int
         _lib.kss_oracle_eval_pod.argtypes = [P(abi.Profile), P(abi.Cluster), P(abi.PodSet), C.c_int,
                                              P(abi.PodResult), C.c_int]
         _lib.kss_oracle_eval_pod.restype = C.c_int
@@ -99,14 +101,22 @@ class Results:
 
 
 def schedule(profile, cluster_struct, podset_struct, n_pods, n_nodes, threads=1, record=True, n_classes=0,
-             n_terms=0, cursor=0, nominations=(), skip_commit=None):
+             n_terms=0, cursor=0, nominations=(), skip_commit=None, ops=None, trace=False):
     """Run the C oracle sequentially; returns (chosen, Results|None, final_state dict).
     record=True keeps every per-node array, record="meta" only the per-pod outcomes.
     cursor: the scheduler's nextStartNodeIndex at the first pod; the final value is
     final_state["next_start"].  nominations: [(pod index, global node)] in the nominator's
     order; final_state["nominations"] lists those still active afterwards.  skip_commit: per pod,
-    evaluated but not assumed (a commit the caller rolled back)."""
+    evaluated and its commit rolled back at once (the node state and the nominator as they were, the
+    assume cache as AssumePodVolumes then RevertAssumedPodVolumes leave it).  ops: a program of steps
+    instead of pods [0, n_pods) -- j >= 0 schedules pod j, -1 - j rolls pod j's commit back; chosen and
+    the results then go by step (a rollback step: the node it left).  trace: final_state["trace"] holds
+    vol_count, vol_attached, pv_owner and claim_node after every step."""
     L = lib()
+    n_all = podset_struct.n_pods
+    if ops is not None:
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        n_pods = len(ops)
     chosen = np.full(max(n_pods, 1), -2, dtype=np.int32)
     res = Results(n_pods, n_nodes, arrays=record is True) if record else None
     N = max(n_nodes, 1)
@@ -123,10 +133,20 @@ def schedule(profile, cluster_struct, podset_struct, n_pods, n_nodes, threads=1,
     nom_pod = np.array([a for a, _ in nominations] or [0], dtype=np.int32)
     nom_node = np.array([b for _, b in nominations] or [0], dtype=np.int32)
     nom_left = np.zeros(max(len(nominations), 1), dtype=np.uint8)
-    skip = np.zeros(max(n_pods, 1), np.uint8)
+    skip = np.zeros(max(n_pods, n_all, 1), np.uint8)
     if skip_commit is not None:
-        skip[:n_pods] = np.asarray(skip_commit, np.uint8)[:n_pods]
-    rc = L.kss_oracle_schedule_wm(C.byref(profile), C.byref(cluster_struct), C.byref(podset_struct), n_pods,
+        sk = np.asarray(skip_commit, np.uint8)
+        skip[:len(sk)] = sk
+    R, K = cluster_struct.n_vol_rows, cluster_struct.n_vol_keys
+    tr = None
+    if trace:
+        tr = dict(vol_count=np.zeros((n_pods, max(R, 1), N), np.int32), vol_attached=np.zeros((n_pods, max(K, 1), N), np.int32),
+                  pv_owner=np.zeros((n_pods, max(cluster_struct.n_pvs, 1)), np.int32),
+                  claim_node=np.zeros((n_pods, max(cluster_struct.n_wclaims, 1)), np.int32))
+
+    def tp(k):
+        return tr[k].ctypes.data_as(P(C.c_int32)) if tr is not None else None
+    rc = L.kss_oracle_schedule_wr(C.byref(profile), C.byref(cluster_struct), C.byref(podset_struct), n_pods,
                                chosen.ctypes.data_as(P(C.c_int32)), res.structs if res else None, threads,
                                st["requested"].ctypes.data_as(P(C.c_int64)), st["nonzero"].ctypes.data_as(P(C.c_int64)),
                                st["pod_count"].ctypes.data_as(P(C.c_int32)),
@@ -138,7 +158,9 @@ def schedule(profile, cluster_struct, podset_struct, n_pods, n_nodes, threads=1,
                                nom_pod.ctypes.data_as(P(C.c_int32)), nom_node.ctypes.data_as(P(C.c_int32)),
                                len(nominations), nom_left.ctypes.data_as(P(C.c_uint8)),
                                st["pv_owner"].ctypes.data_as(P(C.c_int32)), st["claim_node"].ctypes.data_as(P(C.c_int32)),
-                               skip.ctypes.data_as(P(C.c_uint8)))
+                               skip.ctypes.data_as(P(C.c_uint8)),
+                               ops.ctypes.data_as(P(C.c_int32)) if ops is not None else None,
+                               tp("vol_count"), tp("vol_attached"), tp("pv_owner"), tp("claim_node"))
     assert rc == 0, f"oracle rc={rc}"
     st["pv_owner"] = st["pv_owner"][:cluster_struct.n_pvs]
     st["claim_node"] = st["claim_node"][:cluster_struct.n_wclaims]
@@ -146,4 +168,8 @@ def schedule(profile, cluster_struct, podset_struct, n_pods, n_nodes, threads=1,
     st["nominations"] = [e for e, keep in zip(nominations, nom_left) if keep]
     st["vol_count"] = st["vol_count"][:cluster_struct.n_vol_rows, :n_nodes]
     st["vol_attached"] = st["vol_attached"][:cluster_struct.n_vol_keys, :n_nodes]
+    if tr is not None:
+        st["trace"] = dict(vol_count=tr["vol_count"][:, :R], vol_attached=tr["vol_attached"][:, :K],
+                           pv_owner=tr["pv_owner"][:, :cluster_struct.n_pvs],
+                           claim_node=tr["claim_node"][:, :cluster_struct.n_wclaims])
     return chosen[:n_pods], res, st

@@ -5,6 +5,7 @@ attach limits, VolumeBinding PreFilter / Filter, VolumeZone), and against each o
 random clusters with volumes (tests/volume_fuzz.py)."""
 import json
 
+import numpy as np
 import pytest
 
 import edge_fixtures as ef
@@ -229,3 +230,151 @@ def test_random_wffc_clusters_reach_every_branch():
         moved_claim |= bool((fs["claim_node"] != cc.arrays["claim_node"][:len(cc.wclaims)]).any())
     assert {abi.KSS_VB_BIND_CONFLICT} <= details, details
     assert moved_pv and moved_claim
+
+
+# ---------------------------------------------------------------------------------------------
+# Unreserve's RevertAssumedPodVolumes: the assume cache after a rollback that more scheduling follows
+import volume_rollback as vr
+
+ROLLBACK_SEEDS = (100, 109, 111, 113, 116, 121)
+ROLLBACK_ORDERS = {"immediate": lambda n: vr.ops_immediate(n, 3), "lifo": lambda n: vr.ops_lifo(n, 3, 5)}
+
+
+def _c_steps_equal_expect(cc, res, fs, chosen, steps, expect, where):
+    from crosscheck import FILTER_CODE
+    for k, (op, exp) in enumerate(zip(steps, expect)):
+        if op >= 0:
+            assert (cc.node_names[chosen[k]] if chosen[k] >= 0 else "") == exp["selected"], (where, k)
+            want = [0 if exp["filter"][n] is None else FILTER_CODE[exp["filter"][n][0]] for n in cc.node_names]
+            assert [int(f) for f in res.fail_plugin[k, :cc.n_nodes]] == want, (where, k)
+        b, s = vr.decode(cc, fs["trace"]["pv_owner"][k], fs["trace"]["claim_node"][k])
+        assert {c: pv for pv, c in b.items()} == exp["bound"], (where, k)
+        assert s == exp["selected_nodes"], (where, k)
+
+
+@pytest.mark.parametrize("case", ["provisioned_elsewhere", "rebound_same_pv"])
+def test_shared_claim_rollback_matches_hand_derived(case):
+    """fx_wffc_shared_claim_rollback on both oracles, step by step: verdicts, selected nodes and
+    the assume cache after every step equal the literals -- the object oracle's recorded
+    podVolumes, the C oracle's rollback() of the recorded picks, and the C oracle's skip_commit
+    (a commit rolled back at once), which must leave the cache as commit then rollback do."""
+    nodes, bound, pods, steps, expect, st = vf.fx_wffc_shared_claim_rollback()[case]
+    got = vr.run_object_oracle(nodes, bound, pods, st, steps)
+    for k, (g, exp) in enumerate(zip(got, expect)):
+        if g["res"] is not None:
+            ef.check_expect(g["ann"], exp, where=(case, k))
+        assert {c: pv for pv, c in g["bound"].items()} == exp["bound"], (case, k)
+        assert g["selected"] == exp["selected_nodes"], (case, k)
+    cc, cp, _ = compile_cluster(nodes, bound, pods, storage=st)
+    chosen, res, fs = vr.run_c_oracle(cc, cp, steps)
+    assert [int(c) for c in chosen] == [g["chosen"] for g in got]
+    _c_steps_equal_expect(cc, res, fs, chosen, steps, expect, case)
+    # the same sequence as a skipped commit: steps 1 and 2 become one evaluation, not assumed
+    skip = np.zeros(cp.n, np.uint8)
+    skip[1] = 1
+    chosen, res, fs = vr.run_c_oracle(cc, cp, [0, 1, 2], skip_commit=skip)
+    _c_steps_equal_expect(cc, res, fs, chosen, [0, 1, 2], [expect[0], dict(expect[1], **{
+        "bound": expect[2]["bound"], "selected_nodes": expect[2]["selected_nodes"]}), expect[3]], case + " skip")
+
+
+def test_empty_topology_terms_detail_and_cache():
+    """fx_allowed_topologies_empty_terms: the C oracle's VolumeBinding detail per node (the bind
+    conflict wherever no usable term admits the node) and both oracles' final assume cache."""
+    nodes, bound, pods, expect, st = vf.fx_allowed_topologies_empty_terms()
+    cc, cp, _ = compile_cluster(nodes, bound, pods, storage=st)
+    chosen, res, fs = vr.run_c_oracle(cc, cp, list(range(cp.n)))
+    for j, exp in enumerate(expect):
+        for i, n in enumerate(cc.node_names):
+            if exp["vb"][n] == "bind":
+                assert (int(res.fail_plugin[j, i]), int(res.fail_detail[j, i])) == \
+                       (abi.KSS_F_VOLUME_BINDING, abi.KSS_VB_BIND_CONFLICT), (j, n)
+            else:
+                assert int(res.fail_plugin[j, i]) == 0, (j, n)
+    assert vr.decode(cc, fs["pv_owner"], fs["claim_node"]) == ({}, vf.EMPTY_TERMS_FINAL_SELECTED)
+    got = vr.run_object_oracle(nodes, bound, pods, st, list(range(len(pods))))
+    assert (got[-1]["bound"], got[-1]["selected"]) == ({}, vf.EMPTY_TERMS_FINAL_SELECTED)
+
+
+def _rollback_case(seed, order):
+    import volume_fuzz
+    nodes, bound, pods, st = volume_fuzz.make(seed, wffc=True)
+    return nodes, bound, pods, st, ROLLBACK_ORDERS[order](len(pods))
+
+
+@pytest.mark.parametrize("order", sorted(ROLLBACK_ORDERS))
+@pytest.mark.parametrize("seed", ROLLBACK_SEEDS)
+def test_oracles_agree_on_rollback_programs(seed, order):
+    """The rollback fuzz: random WaitForFirstConsumer clusters (pods sharing w-* claims) under a
+    rollback pattern -- immediate (every third pod's commit undone at once) and LIFO (after every
+    five pods the last three undone, newest first).  The object oracle (assume, forget, go on)
+    and the C oracle (commit(), rollback() of the recorded picks) agree on every chosen node,
+    every per-node verdict and on the assume cache after every step."""
+    from crosscheck import FILTER_CODE
+    nodes, bound, pods, st, ops = _rollback_case(seed, order)
+    cc, cp, _ = compile_cluster(nodes, bound, pods, storage=st)
+    got = vr.run_object_oracle(nodes, bound, pods, st, ops)
+    chosen, res, fs = vr.run_c_oracle(cc, cp, ops)
+    for k, (op, g) in enumerate(zip(ops, got)):
+        assert int(chosen[k]) == g["chosen"], (k, op)
+        if op >= 0:
+            for i in range(cc.n_nodes):
+                want = g["res"]["fail"].get(i, "not evaluated")  # (a PreFilter rejection: no node is)
+                code = 0 if want is None else FILTER_CODE.get(want, abi.KSS_F_NOT_EVALUATED)
+                assert int(res.fail_plugin[k, i]) == code, (k, op, i)
+        assert vr.decode(cc, fs["trace"]["pv_owner"][k], fs["trace"]["claim_node"][k]) == \
+               vr.restrict(cc, g["bound"], g["selected"]), (k, op)
+    if order == "immediate":  # the same program as skipped commits (kss_oracle_schedule_wm's skip_commit)
+        n = len(pods)
+        ch2, _, fs2 = vr.run_c_oracle(cc, cp, list(range(n)), record="meta", skip_commit=[j % 3 == 2 for j in range(n)])
+        at = [k for k, op in enumerate(ops) if op >= 0]
+        for j in range(n):
+            k = at[j] + (1 if j % 3 == 2 else 0)  # the step that leaves pod j's state: its rollback, if any
+            assert int(ch2[j]) == int(chosen[at[j]]), j
+            for col in ("pv_owner", "claim_node", "vol_count", "vol_attached"):
+                np.testing.assert_array_equal(fs2["trace"][col][j], fs["trace"][col][k], err_msg=f"pod {j} {col}")
+
+
+def test_rollback_programs_reach_the_shared_claim_cases():
+    """Counted on the object oracle alone, across the seeds and both orders: rollbacks of a pod
+    that provisioned a claim another live pod had statically bound (the claim-keyed revert frees
+    that PV), of a pod that re-bound a PV another live pod had assumed (a skipped commit keeps
+    it), and of a pod holding two delayed claims."""
+    counts = dict(provisioned_others_binding=0, rebound_others_pv=0, two_claims=0, rollbacks=0)
+
+    def on_rollback(o, pod):
+        mine = o.storage.pod_volumes.get(o._key(pod))
+        if mine is None:
+            return
+        counts["rollbacks"] += 1
+        others = [v for k, v in o.storage.pod_volumes.items() if k != o._key(pod)]
+        theirs = [b for v in others for b in v[0]]
+        counts["provisioned_others_binding"] += any(c == key for key in mine[1] for c, _ in theirs)
+        counts["rebound_others_pv"] += any(b in theirs for b in mine[0])
+        counts["two_claims"] += len(mine[0]) + len(mine[1]) >= 2
+    for seed in ROLLBACK_SEEDS:
+        for order in sorted(ROLLBACK_ORDERS):
+            nodes, bound, pods, st, ops = _rollback_case(seed, order)
+            vr.run_object_oracle(nodes, bound, pods, st, ops, on_rollback=on_rollback)
+    print(counts)
+    assert counts["provisioned_others_binding"] >= 1, counts
+    assert counts["rebound_others_pv"] >= 1, counts
+    assert counts["two_claims"] >= 1, counts
+
+
+def test_out_of_order_rollback_pins_the_recorded_form():
+    """The ordering limit of the device's rollback, pinned on the reference.  kss_rollback finds the
+    pod's picks by evaluating FindPodVolumes again, which is exact when the commit being undone is
+    the newest live one (immediate and LIFO rollbacks); upstream keeps podVolumes from Reserve, so
+    a binding cycle may fail after later pods were assumed.  rebound_same_pv with one more step:
+    pod-b assumed pv-x for c-c (step 0), pod-a's Unreserve freed it (2), pod-d assumed it for c-e
+    (3); now pod-b's Unreserve (out of order: pod-d is newer and live) restores pv-x -- in its
+    recorded StaticBindings -- to the snapshot and wipes pod-d's assumption.  Evaluating again
+    would find no PV for c-c (pv-x is c-e's), take c-c for provisioned and leave {c-e: pv-x}."""
+    nodes, bound, pods, steps, _, st = vf.fx_wffc_shared_claim_rollback()["rebound_same_pv"]
+    steps = steps + [-1]
+    got = vr.run_object_oracle(nodes, bound, pods, st, steps)
+    assert got[3]["bound"] == {"pv-x": "c-e"}
+    assert (got[4]["chosen"], got[4]["bound"], got[4]["selected"]) == (0, {}, {})
+    cc, cp, _ = compile_cluster(nodes, bound, pods, storage=st)
+    _, _, fs = vr.run_c_oracle(cc, cp, steps, record=False)
+    assert vr.decode(cc, fs["pv_owner"], fs["claim_node"]) == ({}, {})

@@ -330,7 +330,110 @@ WFFC_FINAL_BINDINGS = {"l-4": "pv-a-5", "l-4b": "pv-b-20", "l-9": "pv-a-10", "w-
 WFFC_FINAL_SELECTED = {"d-1": "b"}
 
 
+# --------------------------------------------------------------------------------------
+# checkVolumeProvisions' allowedTopologies (v1helper.MatchTopologySelectorTerms, v1.26): the terms
+# are ORed; a term without matchLabelExpressions is skipped ("nil or empty term selects no
+# objects"); a term one of whose expressions has no values fails, because its In requirement does
+# not build (labels.NewRequirement: "for 'in', 'notin' operators, values set can't be empty");
+# no terms at all admit every node.  One class per case, one claim per class (no PV of any class:
+# every claim is provisioned), one pod per claim; node c carries no zone label.
+def fx_allowed_topologies_empty_terms():
+    nodes = [node("a", zone="zone-a"), node("b", zone="zone-b"), node("c")]
+
+    def term(zone):
+        return {"matchLabelExpressions": [{"key": ZONE, "values": [zone]}]}
+
+    def tsc(name, terms):
+        return dict(wsc(name, "csi.example.com"), allowedTopologies=terms)
+    st = storage(
+        pvcs=[wpvc("t-1", 1, "empty-then-b"), wpvc("t-2", 1, "empty-only"), wpvc("t-3", 1, "novalues-then-a"),
+              wpvc("t-4", 1, "no-terms")],
+        scs=[tsc("empty-then-b", [{}, term("zone-b")]), tsc("empty-only", [{}]),
+             tsc("novalues-then-a", [{"matchLabelExpressions": [{"key": ZONE, "values": []}]}, term("zone-a")]),
+             tsc("no-terms", [])])
+    pods = [vpod("p1", claim("t-1")),   # {} is skipped, not "matches all": only the zone-b term admits, b
+            vpod("p2", claim("t-2")),   # the only term is skipped: no node is admitted
+            vpod("p3", claim("t-3")),   # the valueless term fails (it is not "matches all" either): zone-a, a
+            vpod("p4", claim("t-4"))]   # no terms: every node; a and b hold one pod each, c none
+    B = ("VolumeBinding", M_VB_BIND)
+    expect = [
+        {"filter": {"a": B, "b": None, "c": B}, "selected": "b", "vb": {"a": "bind", "b": None, "c": "bind"}},
+        {"filter": _all("abc", B), "selected": "", "vb": _all("abc", "bind")},
+        {"filter": {"a": None, "b": B, "c": B}, "selected": "a", "vb": {"a": None, "b": "bind", "c": "bind"}},
+        {"filter": _all("abc"), "selected": "c", "vb": _all("abc")},
+    ]
+    return nodes, [], pods, expect, st
+
+
+# the assume cache after the fixture's pods: nothing bound, every scheduled pod's claim selected
+EMPTY_TERMS_FINAL_SELECTED = {"t-1": "b", "t-3": "a", "t-4": "c"}
+
+
+# --------------------------------------------------------------------------------------
+# Unreserve's RevertAssumedPodVolumes(podVolumes) (v1.26 binder.go) with a claim two pods share:
+# it restores to the informer's objects exactly the PVs in the rolled-back pod's own StaticBindings
+# (pvCache.Restore) and the claims in its own DynamicProvisions (pvcCache.Restore) -- also where
+# another assumed pod had set the same PV or claim -- and nothing else.
+#
+# Nodes a1 a2 (zone-a), b1 b2 (zone-b); one CSI WaitForFirstConsumer class without
+# allowedTopologies (provisioning is admitted everywhere); PV pv-x (5Gi, zone-a affinity); claims
+# c-c and c-e (5Gi each); every pod pinned to a zone by nodeSelector (NodeAffinity fails the other
+# zone's nodes before VolumeBinding runs).  Per case (nodes, bound, pods, steps, expect, storage):
+# a step j >= 0 schedules and assumes pods[j], -1 - j is pod j's Unreserve; expect[k] gives step
+# k's per-node verdict and selected node (schedule steps) and the assume cache after the step
+# ("bound": claim -> PV, "selected": claim -> node).
+#
+# provisioned_elsewhere (what the claim-keyed revert gets wrong):
+#   0  B (c-c, zone-a): pv-x matches on a1 a2; a1 (ties: lowest index).  pv-x is assumed for c-c.
+#   1  A (c-c, zone-b): FindMatchingVolume finds pv-x bound to c-c and returns nothing, its affinity
+#      failing on b1 b2: c-c is provisioned; b1.  A's podVolumes: no static binding, provision c-c.
+#   2  Unreserve A: only c-c's selected node goes back (none in the snapshot).  pv-x stays B's:
+#      restoring "every PV of the pod's claims" frees it here.
+#   3  D (c-e, zone-a): pv-x belongs to c-c, so nothing matches and c-e is provisioned; a2 (a1 holds
+#      B).  With pv-x wrongly freed D would bind it: bound {c-e: pv-x}, nothing selected.
+# rebound_same_pv (what "commit then rollback is a no-op" gets wrong):
+#   0  B as above: a1, pv-x assumed for c-c.
+#   1  A (c-c, zone-a): FindMatchingVolume returns pv-x again (bound to c-c, affinity holds); a2
+#      (a1 holds B).  A's podVolumes: static binding pv-x.
+#   2  Unreserve A: pv-x goes back to the snapshot's object, unbound -- B's assumption is wiped.
+#   3  D (c-e, zone-a): pv-x is free and matches; a2 (A left it).  pv-x is assumed for c-e.  Had step
+#      1-2 been skipped, pv-x would still be c-c's and c-e provisioned: bound {c-c: pv-x}, c-e on a2.
+def fx_wffc_shared_claim_rollback():
+    nodes = [node("a1", zone="zone-a"), node("a2", zone="zone-a"), node("b1", zone="zone-b"),
+             node("b2", zone="zone-b")]
+
+    def st():
+        return storage(pvs=[wpv("pv-x", 5, "late", zone="zone-a")], pvcs=[wpvc("c-c", 5, "late"), wpvc("c-e", 5, "late")],
+                       scs=[wsc("late", "csi.example.com")])
+
+    def zpod(name, claim_name, zone):
+        p = vpod(name, claim(claim_name))
+        p["spec"]["nodeSelector"] = {ZONE: zone}
+        return p
+    AFF = ("NodeAffinity", "node(s) didn't match Pod's node affinity/selector")
+    in_a = {"a1": None, "a2": None, "b1": AFF, "b2": AFF}
+    in_b = {"a1": AFF, "a2": AFF, "b1": None, "b2": None}
+    steps = [0, 1, -2, 2]
+    elsewhere = [zpod("pod-b", "c-c", "zone-a"), zpod("pod-a", "c-c", "zone-b"), zpod("pod-d", "c-e", "zone-a")]
+    expect_elsewhere = [
+        {"filter": in_a, "selected": "a1", "bound": {"c-c": "pv-x"}, "selected_nodes": {}},
+        {"filter": in_b, "selected": "b1", "bound": {"c-c": "pv-x"}, "selected_nodes": {"c-c": "b1"}},
+        {"bound": {"c-c": "pv-x"}, "selected_nodes": {}},
+        {"filter": in_a, "selected": "a2", "bound": {"c-c": "pv-x"}, "selected_nodes": {"c-e": "a2"}},
+    ]
+    same = [zpod("pod-b", "c-c", "zone-a"), zpod("pod-a", "c-c", "zone-a"), zpod("pod-d", "c-e", "zone-a")]
+    expect_same = [
+        {"filter": in_a, "selected": "a1", "bound": {"c-c": "pv-x"}, "selected_nodes": {}},
+        {"filter": in_a, "selected": "a2", "bound": {"c-c": "pv-x"}, "selected_nodes": {}},
+        {"bound": {}, "selected_nodes": {}},
+        {"filter": in_a, "selected": "a2", "bound": {"c-e": "pv-x"}, "selected_nodes": {}},
+    ]
+    return {"provisioned_elsewhere": (nodes, [], elsewhere, steps, expect_elsewhere, st()),
+            "rebound_same_pv": (nodes, [], same, steps, expect_same, st())}
+
+
 FIXTURES = {
+    "allowed_topologies_empty_terms": fx_allowed_topologies_empty_terms,
     "disk_conflict": fx_disk_conflict,
     "non_csi_limits": fx_non_csi_limits,
     "csi_limits": fx_csi_limits,
