@@ -478,7 +478,10 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * of the ports-and-images form, and the service grid evaluates it on its k_simple-shaped chain
  * (kss_service_mode 1 / 2, kss_service_form 1) under that chain's other conditions, provided no
  * pod has a volume program and every pod's preferred NodeAffinity weights sum to at most 8191;
- * which kernel a staged batch runs on does not follow it; kss_plan_service follows it).  Read when a context is created (shards, xcd, xcd_shards,
+ * which kernel a staged batch runs on does not follow it; kss_plan_service follows it),
+ * "sweep_ports_images" (default 0, independent of the four above; 1: a scenario sweep whose pods
+ * hold host ports or node-cached images is staged instead of refused -- see kss_sweep_create;
+ * a sweep without such a pod is staged and launched as with 0; kss_plan_sweep follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -716,14 +719,37 @@ int kss_schedule_scenarios(int32_t device, const kss_profile* prof, int32_t n_sc
  * snapshot on the device and schedules all of them (chosen_out [sum n_pods]; device_ms =
  * reset + launches, HIP events).  Replaces, per scenario, the sequential scheduleOne
  * loop of the simulator's scheduler; the scenario axis of SURVEY 8(e).
- * kss_sweep_info: host wall time of create (pack + upload), the kernel used (1 k_simple,
- * 0 k_schedule) and the uploaded bytes. */
+ * kss_sweep_info: host wall time of create (pack + upload), the kernel used (1 the k_simple
+ * family, 0 k_schedule) and the uploaded bytes.
+ *
+ * Pods with host ports (NodePorts) or node-cached images (ImageLocality): refused
+ * (KSS_E_UNSUPPORTED) while the process-wide option "sweep_ports_images" is 0.  With 1, a sweep in
+ * which some scenario holds such a pod runs in the ports-and-images form (kss_sweep_form 1): every
+ * scenario's image-score rows are packed with its inputs and its UsedPorts column with its mutable
+ * state (restored by every kss_sweep_run; a cluster without a port dictionary gets a zero column),
+ * nothing shared between scenarios.  The form is one decision for the whole sweep: it runs on
+ * k_static_pi + k_simple_pi_sweep (kernel 1) when every scenario meets k_simple's conditions and
+ * every pod's positive preferred NodeAffinity weights sum to at most 8191, else on k_schedule
+ * (kernel 0).  A sweep without such a pod keeps its layout, upload_bytes and kernels whatever
+ * the option says.  A pod with a volume program refuses the sweep with either value. */
 typedef struct kss_sweep kss_sweep;
 kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_scen, const kss_cluster* clusters,
                             const kss_podset* podsets);
 int kss_sweep_run(kss_sweep* sw, int32_t* chosen_out, double* device_ms);
 int kss_sweep_info(kss_sweep* sw, double* stage_ms, int32_t* kernel, int64_t* upload_bytes);
+/* 1 when the sweep runs in the ports-and-images form, 0 otherwise; <0 on error */
+int kss_sweep_form(kss_sweep* sw);
 void kss_sweep_destroy(kss_sweep* sw);
+/* Host only (no device): the routing kss_sweep_create would choose for these scenarios under
+ * `prof` and the process-wide option "sweep_ports_images" -- the same function decides both.
+ * out[0] = kernel (1 the k_simple family, 0 k_schedule), out[1] = 1 the ports-and-images form,
+ * out[2], out[3] = the first scenario and pod that keep the sweep off the k_simple family or refuse
+ * it (-1: none, or no single one).  Returns the reason code (>= 0: kss_plan_reason; 0 eligible),
+ * or a negative KSS_E_* exactly where kss_sweep_create would fail: KSS_E_UNSUPPORTED for a pod with
+ * a volume program (either option value) and for a pod with host ports or image rows with the
+ * option 0 (kss_last_error names which; out[2], out[3] name the pod). */
+int kss_plan_sweep(const kss_profile* prof, int32_t n_scen, const kss_cluster* clusters, const kss_podset* podsets,
+                   int32_t out[4]);
 
 /* ---- node-axis sharding ----------------------------
  * One context per GPU holds rows [lo, hi) of the cluster (node_base = lo); the pods are
@@ -967,9 +993,10 @@ int kss_abi_sizes(int32_t* out, int32_t n);
  * pod's reason as before, or the reason naming the 8191 limit and its pod).  A batch of such pods
  * WITH spread / inter-pod programs follows the option "spread_ports_images" instead: 1 plans it on
  * k_spread (its ports-and-images form) under the same two conditions and with the option "fold" 0
- * (the 8191 limit has a reason of its own there, naming k_spread).  Sweeps, the split grid, the node
- * axis refuse such pods whatever the options say; the service grid follows an option of its own,
- * "service_ports_images" (kss_plan_service), which changes nothing here.  The
+ * (the 8191 limit has a reason of its own there, naming k_spread).  The split grid and the node
+ * axis refuse such pods whatever the options say; the service grid and scenario sweeps follow
+ * options of their own, "service_ports_images" (kss_plan_service) and "sweep_ports_images"
+ * (kss_plan_sweep), which change nothing here.  The
  * option "table_images" changes nothing here: with or without the shape table the kernel is
  * k_simple. */
 int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3);

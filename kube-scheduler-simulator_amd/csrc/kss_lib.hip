@@ -82,7 +82,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_N
 };
 struct OptDef {
   const char* name;
@@ -124,6 +124,7 @@ const OptDef kOptDefs[O_N] = {
     {"table_images", "KSS_TABLE_IMAGES", 0},                // that form's batches without a host-port pod on the shape-table loop
     {"spread_ports_images", "KSS_SPREAD_PORTS_IMAGES", 0},  // k_spread's ports-and-images form (independent of simple_ports_images)
     {"service_ports_images", "KSS_SERVICE_PORTS_IMAGES", 0},  // the service grid's k_simple-shaped chain for such pods (independent of the three above)
+    {"sweep_ports_images", "KSS_SWEEP_PORTS_IMAGES", 0},  // scenario sweeps admit such pods: k_simple_pi_sweep or k_schedule (independent of the four above)
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -495,6 +496,8 @@ __global__ __launch_bounds__(256) void k_handoff_final(const DevJob* __restrict_
 // instantiations (spread_pi_fn) at the end of this file
 __global__ void k_handoff_final_pi(const DevJob* __restrict__ jobs, int W, int w_off, int n_res, HandoffCheck hc, int* err);
 static const void* spread_pi_fn(bool def, bool lb, bool win);
+// ... and k_simple_pi_sweep<DEF>, the ports-and-images form of a scenario sweep, behind those
+static const void* simple_pi_sweep_fn(bool def);
 
 // Static words of pods [k0, min(k1, n_pods)) x every node of every job.  grid: x = 1024-node
 // tiles, y = groups of STATIC_PODS pods, z = job.  One lane per QUAD of adjacent nodes walks its
@@ -862,6 +865,7 @@ struct GpodNeeds {
 // Per-batch LDS / exchange sizing: the host restatement of make_plan's bin counts.
 struct PlanNeeds {
   bool ports_images = false;  // some pod has host ports, ImageLocality rows or a volume program
+  bool volumes = false;       // ... a volume program (the part of ports_images no sweep takes)
   int bins_cap = 0;  // max over pods of histogram + presence bins
   int xw = 0;        // max exchange payload length (values) over pods and exchanges
   bool general = false;  // some pod carries spread / inter-pod-affinity programs
@@ -1350,13 +1354,17 @@ struct PiRecords {
 // svc (staging only): the option service_ports_images asks for that form as well -- the service
 // grid reads the staged records; which kernel a staged batch runs on still follows
 // simple_ports_images alone (run_single).
+// force (a scenario of a sweep in that form, sweep_plan): records of the form whatever the options
+// and the pods say -- one launch serves every scenario, so a scenario without such a pod gets them
+// too, with zero masks.
 bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr,
-                 PiRecords* pi = nullptr, bool svc = false) {
+                 PiRecords* pi = nullptr, bool svc = false, bool force = false) {
   out.assign((size_t)std::max(ps->n_pods, 1), SPod{});
   if (n_shapes) *n_shapes = 0;
   bool form = false;
   if (pi) {
     *pi = PiRecords{};
+    form = force;
     if (opt(O_SIMPLE_PI) || (svc && opt(O_SERVICE_PI)))
       for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
     pi->form = form;
@@ -1422,6 +1430,11 @@ enum {
   GP_SVC_PI_NA_WEIGHTS,
   GP_SVC_SCALAR,
   GP_SVC_PCT_NAMES,
+  GP_SWEEP_PROGRAMS,
+  GP_SWEEP_SCALAR,
+  GP_SWEEP_PCT,
+  GP_SWEEP_VALUES,
+  GP_SWEEP_GEOMETRY,
   GP_NCODES
 };
 const char* const kGpReason[GP_NCODES] = {
@@ -1454,6 +1467,11 @@ const char* const kGpReason[GP_NCODES] = {
     "ports-and-images form keeps 13 bits of raw NodeAffinity): the service's general chain",
     "the cluster has extended (scalar) resources: the service's general chain",
     "percentageOfNodesToScore below 100 with a NodeAffinity PreFilterResult list: the service's general chain",
+    "spread / inter-pod-affinity programs in a scenario: the whole sweep runs on k_schedule",
+    "a scenario's cluster has extended (scalar) resources: the whole sweep runs on k_schedule",
+    "percentageOfNodesToScore below 100: the whole sweep runs on k_schedule",
+    "a scenario's values or the profile's weights leave the exact f64 envelope: the whole sweep runs on k_schedule",
+    "the option no_simple, or the largest scenario does not fit one workgroup's LDS: the whole sweep runs on k_schedule",
 };
 
 bool gfail(GpodNeeds& need, int code, int pod) {
@@ -2841,6 +2859,7 @@ static PlanNeeds plan_needs(const int32_t* key_card, const uint32_t* key_flags, 
     int bins = 0, hp = 0, sp = 0;
     if (p.n_hard | p.n_soft | p.ipa_len) r.general = true;
     if (p.port_conflict | p.port_add || p.img_len > 0 || p.vol_len > 0) r.ports_images = true;
+    if (p.vol_len > 0) r.volumes = true;
     for (int h = 0; h < p.n_hard && h < MAXH; h++) {
       const int key = ps->spreads[p.spread_off + h].key;
       if (!(key_flags[key] & KSS_KEY_UNIQUE)) {
@@ -3103,10 +3122,16 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          unsigned long long* stamps = nullptr, hipEvent_t* ev = nullptr, const SplitRun* split = nullptr,
                          int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
                          hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
-                         int n_shapes = 0, bool flat = false, const SPort* sports = nullptr) {
+                         int n_shapes = 0, bool flat = false, const SPort* sports = nullptr,
+                         const int32_t* pod_off = nullptr) {
   // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
   // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
   const bool pi = sports != nullptr;
+  // ... of a sweep (many jobs; pod_off: every job's first mask in sports): k_static_pi +
+  // k_simple_pi_sweep.  No table, no window, no split and no XCD-local grid: sweeps pass none of those.
+  const bool pi_sweep = pi && pod_off != nullptr;
+  if (pi_sweep && (n_shapes > 0 || k_find > 0 || split || xcd || nsc != 0))
+    return fail(KSS_E_INVAL, "sweep ports-and-images form: no table, window, split or XCD-local grid");
   // st2 (with pev, two events per chunk): the static words of chunk i+1 are computed on st2 into the
   // other half of a double-buffered table while k_simple runs chunk i on st (each job's table holds
   // 2 x chunk rows); k_simple of chunk i waits for its k_static, k_static of chunk i+1 for
@@ -3124,7 +3149,8 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
   if (flat && gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
     return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
-  const void* fn = flat  ? (pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat)
+  const void* fn = pi_sweep ? simple_pi_sweep_fn(def)
+                   : flat  ? (pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat)
                    : tab ? (pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab)
                    : pi  ? (win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
                                 : (def ? (const void*)k_simple_pi<true, false> : (const void*)k_simple_pi<false, false>))
@@ -3183,7 +3209,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     unsigned long long* sp = k0 == 0 ? stamps : nullptr;
     void* args[] = {(void*)&jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
                     (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg,
-                    (void*)&sports};  // (k_simple_pi's trailing argument; the other kernels take 13)
+                    (void*)&sports, (void*)&pod_off};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's two; the other kernels take 13)
     const int ci = k0 / chunk;
     if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
     if (xcd) {
@@ -4977,8 +5003,10 @@ struct Packer {
 };
 
 // The read-only part of one scenario: cluster columns except the mutable ones, the pod
-// programs and (simple sweeps) the compact pod records.
-void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const std::vector<SPod>* spods, DevJob& j) {
+// programs and (simple sweeps) the compact pod records.  pi (a sweep in the ports-and-images form):
+// + the image-score rows.
+void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const std::vector<SPod>* spods, DevJob& j,
+                 bool pi = false) {
   const size_t N = (size_t)cl->n_nodes, K = (size_t)cl->n_label_keys;
   DevCluster& c = j.c;
   c.N = cl->n_nodes;
@@ -5011,7 +5039,11 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
   c.nct = nullptr;
   c.nc32 = nullptr;
   c.ncl = nullptr;
-  c.n_vol_rows = c.n_vol_keys = 0;  // sweeps refuse pods with volume programs (ports_images)
+  if (pi) {
+    c.image_score = P.put(cl->image_score, (size_t)cl->n_images * N);
+    c.n_images = cl->n_images;
+  }
+  c.n_vol_rows = c.n_vol_keys = 0;  // sweeps refuse pods with volume programs (sweep_plan)
   c.vol_count = c.vol_attached = nullptr;
   c.vol_limit = c.vol_row_key = c.vol_key_plugin = nullptr;
   j.P.vols = nullptr;
@@ -5025,14 +5057,16 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
 }
 
 // The mutable columns of one scenario (AssumePod targets): the host image holds the
-// snapshot (the device's pristine copy); the device pointers address the live copy.
-void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j) {
+// snapshot (the device's pristine copy); the device pointers address the live copy.  pi: + the
+// UsedPorts column (zero without a port dictionary), restored with the rest on every run.
+void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j, bool pi = false) {
   const size_t N = (size_t)cl->n_nodes;
   j.c.requested = P.put(cl->requested, KSS_NRES * N);
   j.c.nonzero = P.put(cl->nonzero, 2 * N);
   j.c.pod_count = P.put(cl->pod_count, N);
   j.c.class_count = P.put(cl->class_count, (size_t)cl->n_classes * N);
   j.c.term_count = P.put(cl->term_count, (size_t)cl->n_terms * N);
+  if (pi) j.c.port_used = P.put<uint64_t>(cl->n_ports > 0 ? cl->port_used : nullptr, N);
 }
 
 }  // namespace
@@ -5052,6 +5086,8 @@ struct kss_sweep {
   std::vector<int32_t> n_pods;
   int total_pods = 0, max_pods = 0, max_nodes = 0, max_keys = 0;
   bool simple = false;
+  bool form = false;  // the ports-and-images form (option sweep_ports_images): both columns packed
+  size_t sports_off = 0, podoff_off = 0;  // form on the k_simple family: SPort[total_pods + RING], int32[n_scen]
   int chunk = 0;
   Geometry g;
   PlanNeeds need;
@@ -5069,6 +5105,116 @@ struct kss_sweep {
 
 extern "C" {
 
+// The routing of a whole sweep (kss_plan_sweep and kss_sweep_create: one function, so the two
+// cannot disagree).  One launch serves every scenario, so the kernel and the form are one decision:
+//   - a pod with a volume program refuses the sweep (pack_inputs zeroes the volume columns), and so
+//     does a pod with host ports or image rows while the option sweep_ports_images is 0;
+//   - form: the option is on and some scenario holds such a pod.  Then every scenario gets records
+//     of the ports-and-images form (build_spods force: its 13-bit limit on raw NodeAffinity, zero
+//     masks for pods without ports) and the kernel is k_simple_pi_sweep;
+//   - whatever keeps one scenario off the k_simple family (code, scen, pod: the first) puts the
+//     whole sweep on k_schedule, which reads the packed columns through DevCluster.
+// Needs no device.
+struct SweepPlan {
+  bool simple = false, form = false;
+  int code = GP_OK, scen = -1, pod = -1;  // why k_schedule / why refused, and where
+  int total_pods = 0, max_pods = 0, max_nodes = 0, max_keys = 0;
+  Geometry g;
+  PlanNeeds need;
+  std::vector<std::vector<SPod>> spods;  // simple: every scenario's records
+  std::vector<SPort> sports;             // simple && form: the masks in the order of `chosen`, + RING of padding
+  std::vector<int32_t> pod_off;          // ... and every scenario's first
+};
+
+static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* clusters, const kss_podset* podsets,
+                      SweepPlan& pl) {
+  pl = SweepPlan{};
+  const bool allow = opt(O_SWEEP_PI) != 0;
+  for (int s = 0; s < n_scen; s++) {
+    pl.total_pods += podsets[s].n_pods;
+    pl.max_pods = std::max(pl.max_pods, podsets[s].n_pods);
+    pl.max_nodes = std::max(pl.max_nodes, clusters[s].n_nodes);
+    pl.max_keys = std::max(pl.max_keys, clusters[s].n_label_keys);
+    const PlanNeeds q = plan_needs(clusters[s].key_card, clusters[s].key_flags, &podsets[s], podsets[s].n_pods);
+    pl.need.bins_cap = std::max(pl.need.bins_cap, q.bins_cap);
+    pl.need.general |= q.general;
+    if (q.volumes || (q.ports_images && !allow)) {  // the first refusing pod; a volume pod before the others
+      for (int i = 0; i < podsets[s].n_pods; i++) {
+        const kss_pod& p = podsets[s].pods[i];
+        if (q.volumes ? p.vol_len > 0 : pod_ports_images(p)) {
+          pl.scen = s;
+          pl.pod = i;
+          pl.code = GP_PORTS_IMAGES;
+          if (q.volumes)
+            return fail(KSS_E_UNSUPPORTED,
+                        "scenario sweeps: pods with volumes (a volume program) take kss_schedule_batch, one scenario at a "
+                        "time, whatever the option sweep_ports_images says");
+          return fail(KSS_E_UNSUPPORTED,
+                      "scenario sweeps: pods with host ports or ImageLocality rows (node-cached images) take "
+                      "kss_schedule_batch, one scenario at a time, or the option sweep_ports_images = 1");
+        }
+      }
+    }
+    pl.form |= q.ports_images;  // (no volumes here, and the option is on)
+  }
+  // one workgroup per scenario: at most two node slots per lane (C5, 1,000 nodes: 512
+  // threads ran the 512-scenario sweep in 16.5 ms against 23.7 ms at 256)
+  int pref = pl.max_nodes > 512 ? 512 : 256;
+  if (opt(O_THREADS) > 0) pref = (int)std::min<long long>(KSS_MAX_THREADS, std::max(64ll, opt(O_THREADS)));
+  if (!pick_geometry(pl.max_nodes, 1, pref, pl.g)) return fail(KSS_E_UNSUPPORTED, "scenario cluster too large for one workgroup");
+  // k_static + k_simple for the whole sweep when every scenario qualifies (no spread /
+  // inter-pod programs, no scalar resources, values inside the exact f64 envelope); in the form,
+  // k_static_pi + k_simple_pi_sweep within that kernel's LDS
+  auto demote = [&](int code, int scen, int pod) {
+    pl.code = code;
+    pl.scen = scen;
+    pl.pod = pod;
+    return 0;
+  };
+  if (opt(O_NO_SIMPLE) || !simple_fits(pl.g, 0, pl.form)) return demote(GP_SWEEP_GEOMETRY, -1, -1);
+  if (pl.need.general) {
+    for (int s = 0; s < n_scen; s++)
+      for (int i = 0; i < podsets[s].n_pods; i++)
+        if (podsets[s].pods[i].n_hard | podsets[s].pods[i].n_soft | podsets[s].pods[i].ipa_len)
+          return demote(GP_SWEEP_PROGRAMS, s, i);
+  }
+  if (prof->pct_nodes_to_score < 100) return demote(GP_SWEEP_PCT, -1, -1);  // the window runs on k_schedule
+  for (int i = 0; i < prof->fit_n; i++)
+    if (!(prof->fit_weight[i] >= 0 && prof->fit_weight[i] < (1ll << 20))) return demote(GP_SWEEP_VALUES, -1, -1);
+  pl.spods.resize((size_t)n_scen);
+  if (pl.form) pl.sports.reserve((size_t)pl.total_pods + RING);
+  for (int s = 0; s < n_scen; s++) {
+    const kss_cluster& cl = clusters[s];
+    if (cl.n_scalar != 0) return demote(GP_SWEEP_SCALAR, s, -1);
+    for (size_t i = 0; i < 3 * (size_t)cl.n_nodes; i++)
+      if (!(cl.alloc[i] >= 0 && cl.alloc[i] < (1ll << 46))) return demote(GP_SWEEP_VALUES, s, -1);
+    F64Bounds bc, bp;
+    f64_bounds_cluster(&cl, bc);
+    f64_bounds_pods(&podsets[s], bp);
+    if (!f64_exact(bc, bp, podsets[s].n_pods)) return demote(GP_SWEEP_VALUES, s, -1);
+    PiRecords pi;
+    if (!build_spods(&podsets[s], 0, pl.spods[s], nullptr, pl.form ? &pi : nullptr, false, pl.form)) {
+      // (no programs, no volumes: fill_spod refused a pod's preferred NodeAffinity weights)
+      const int64_t lim = pl.form ? (int64_t)SWPI_NA_MAX : 0xFFFFF;
+      for (int i = 0; i < podsets[s].n_pods; i++) {
+        const kss_pod& p = podsets[s].pods[i];
+        int64_t wsum = 0;
+        for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, podsets[s].terms[p.pref_off + t].weight);
+        if (wsum > lim) return demote(wsum > 0xFFFFF ? GP_NA_WEIGHTS : GP_PI_NA_WEIGHTS, s, i);
+      }
+      return demote(GP_NA_WEIGHTS, s, -1);
+    }
+    if (pl.form) {
+      pl.pod_off.push_back((int32_t)pl.sports.size());
+      pl.sports.insert(pl.sports.end(), pi.ports.begin(), pi.ports.begin() + podsets[s].n_pods);
+    }
+  }
+  // the ring's prefetch distance of padding: the last scenario's prefetch stays inside the allocation
+  if (pl.form) pl.sports.resize((size_t)pl.total_pods + RING, SPort{});
+  pl.simple = true;
+  return 0;
+}
+
 kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_scen, const kss_cluster* clusters,
                             const kss_podset* podsets) {
   if (!prof || n_scen <= 0 || !clusters || !podsets) {
@@ -5084,63 +5230,42 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   sw->prof = *prof;
   sw->n_scen = n_scen;
   sw->n_pods.resize(n_scen);
-  for (int s = 0; s < n_scen; s++) {
-    sw->n_pods[s] = podsets[s].n_pods;
-    sw->total_pods += podsets[s].n_pods;
-    sw->max_pods = std::max(sw->max_pods, podsets[s].n_pods);
-    sw->max_nodes = std::max(sw->max_nodes, clusters[s].n_nodes);
-    sw->max_keys = std::max(sw->max_keys, clusters[s].n_label_keys);
-    const PlanNeeds q = plan_needs(clusters[s].key_card, clusters[s].key_flags, &podsets[s], podsets[s].n_pods);
-    sw->need.bins_cap = std::max(sw->need.bins_cap, q.bins_cap);
-    sw->need.general |= q.general;
-    if (q.ports_images) {  // the sweep packs no UsedPorts / image-score columns
-      fail(KSS_E_UNSUPPORTED, "scenario sweeps: pods with host ports, ImageLocality rows or volumes take kss_schedule_batch");
-      return nullptr;
-    }
-  }
-  // one workgroup per scenario: at most two node slots per lane (C5, 1,000 nodes: 512
-  // threads ran the 512-scenario sweep in 16.5 ms against 23.7 ms at 256)
-  int pref = sw->max_nodes > 512 ? 512 : 256;
-  if (opt(O_THREADS) > 0) pref = (int)std::min<long long>(KSS_MAX_THREADS, std::max(64ll, opt(O_THREADS)));
-  if (!pick_geometry(sw->max_nodes, 1, pref, sw->g)) {
-    fail(KSS_E_UNSUPPORTED, "scenario cluster too large for one workgroup");
-    return nullptr;
-  }
-  // k_static + k_simple for the whole sweep when every scenario qualifies (no spread /
-  // inter-pod programs, no scalar resources, values inside the exact f64 envelope)
-  std::vector<std::vector<SPod>> spods(n_scen);
-  bool simple = !opt(O_NO_SIMPLE) && !sw->need.general && simple_fits(sw->g, 0) &&
-                prof->pct_nodes_to_score >= 100;  // the window runs on k_schedule
-  for (int i = 0; i < prof->fit_n && simple; i++) simple = prof->fit_weight[i] >= 0 && prof->fit_weight[i] < (1ll << 20);
-  for (int s = 0; s < n_scen && simple; s++) {
-    const kss_cluster& cl = clusters[s];
-    simple = cl.n_scalar == 0;
-    for (size_t i = 0; i < 3 * (size_t)cl.n_nodes && simple; i++) simple = cl.alloc[i] >= 0 && cl.alloc[i] < (1ll << 46);
-    if (simple) {
-      F64Bounds bc, bp;
-      f64_bounds_cluster(&cl, bc);
-      f64_bounds_pods(&podsets[s], bp);
-      simple = f64_exact(bc, bp, podsets[s].n_pods);
-    }
-    if (simple) simple = build_spods(&podsets[s], 0, spods[s]);
-  }
-  sw->simple = simple;
+  for (int s = 0; s < n_scen; s++) sw->n_pods[s] = podsets[s].n_pods;
+  SweepPlan pl;
+  if (sweep_plan(prof, n_scen, clusters, podsets, pl)) return nullptr;
+  sw->total_pods = pl.total_pods;
+  sw->max_pods = pl.max_pods;
+  sw->max_nodes = pl.max_nodes;
+  sw->max_keys = pl.max_keys;
+  sw->need = pl.need;
+  sw->g = pl.g;
+  sw->simple = pl.simple;
+  sw->form = pl.form;
+  const bool simple = pl.simple, form = pl.form;
+  std::vector<std::vector<SPod>>& spods = pl.spods;
   // layout: [inputs][pristine state][jobs] uploaded; [live state][chosen][meta][err][gran][stat]
+  // (the form on the k_simple family: [masks][pod offsets] behind the jobs, uploaded with them)
   std::vector<DevJob> jobs(n_scen);
   std::vector<size_t> in_off(n_scen), mut_off(n_scen);
   Packer dry;
   for (int s = 0; s < n_scen; s++) {
     in_off[s] = dry.o;
-    pack_inputs(dry, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s]);
+    pack_inputs(dry, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form);
   }
   sw->pristine_off = dry.o;
   for (int s = 0; s < n_scen; s++) {
     mut_off[s] = dry.o;
-    pack_mutable(dry, &clusters[s], jobs[s]);
+    pack_mutable(dry, &clusters[s], jobs[s], form);
   }
   sw->mut_bytes = dry.o - sw->pristine_off;
   sw->jobs_off = dry.o;
   dry.put<DevJob>(nullptr, (size_t)n_scen);
+  if (form && simple) {
+    dry.put<SPort>(nullptr, pl.sports.size());
+    sw->sports_off = dry.last;
+    dry.put<int32_t>(nullptr, (size_t)n_scen);
+    sw->podoff_off = dry.last;
+  }
   sw->up_bytes = dry.o;
   sw->live_off = dry.o;
   dry.o = align_up(dry.o + sw->mut_bytes, 256);
@@ -5189,10 +5314,10 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   auto work = [&](int t) {
     for (int s = t; s < n_scen; s += nth) {
       Packer P{img.get(), sw->arena, in_off[s]};
-      pack_inputs(P, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s]);
+      pack_inputs(P, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form);
       // host bytes at the pristine position, device pointers at the live position
       Packer M{img.get(), sw->arena + (sw->live_off - sw->pristine_off), mut_off[s]};
-      pack_mutable(M, &clusters[s], jobs[s]);
+      pack_mutable(M, &clusters[s], jobs[s], form);
       DevJob& j = jobs[s];
       j.n_pods = podsets[s].n_pods;
       j.commit = 1;
@@ -5220,6 +5345,10 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
     }
   }
   memcpy(img.get() + sw->jobs_off, jobs.data(), sizeof(DevJob) * n_scen);
+  if (form && simple) {
+    memcpy(img.get() + sw->sports_off, pl.sports.data(), sizeof(SPort) * pl.sports.size());
+    memcpy(img.get() + sw->podoff_off, pl.pod_off.data(), sizeof(int32_t) * pl.pod_off.size());
+  }
   if (hipMemcpy(sw->arena, img.get(), sw->up_bytes, hipMemcpyHostToDevice) != hipSuccess) {
     fail(KSS_E_DEVICE, "sweep upload failed");
     return nullptr;
@@ -5253,7 +5382,9 @@ int kss_sweep_run(kss_sweep* sw, int32_t* chosen_out, double* device_ms) {
   int rc;
   if (sw->simple)
     rc = launch_simple(st, sw->g, sw->n_scen, jobs, sw->prof, sw->max_pods, sw->max_nodes, sw->chunk, nullptr, 0, err, nullptr,
-                       nullptr, nullptr, 0, false, nullptr, sw->max_keys, sw->st2, &sw->pev);
+                       nullptr, nullptr, 0, false, nullptr, sw->max_keys, sw->st2, &sw->pev, 0, 0, false,
+                       sw->form ? reinterpret_cast<const SPort*>(sw->arena + sw->sports_off) : nullptr,
+                       sw->form ? reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off) : nullptr);
   else
     rc = launch_schedule(st, sw->g, sw->n_scen, sw->need.bins_cap + (sw->prof.pct_nodes_to_score < 100 ? 1 : 0),
                          sw->need.general, sw->max_keys, jobs, sw->prof, nullptr, err);
@@ -5286,6 +5417,11 @@ int kss_sweep_info(kss_sweep* sw, double* stage_ms, int32_t* kernel, int64_t* up
   if (kernel) *kernel = sw->simple ? 1 : 0;
   if (upload_bytes) *upload_bytes = (int64_t)sw->up_bytes;
   return 0;
+}
+
+int kss_sweep_form(kss_sweep* sw) {
+  if (!sw) return fail(KSS_E_INVAL, "null sweep");
+  return sw->form ? 1 : 0;
 }
 
 void kss_sweep_destroy(kss_sweep* sw) {
@@ -5743,6 +5879,23 @@ int kss_plan_service(const kss_cluster* cl, const kss_podset* ps, const kss_prof
   return 0;
 }
 
+int kss_plan_sweep(const kss_profile* prof, int32_t n_scen, const kss_cluster* clusters, const kss_podset* podsets,
+                   int32_t out[4]) {
+  if (!prof || n_scen <= 0 || !clusters || !podsets || !out) return fail(KSS_E_INVAL, "bad arguments");
+  if (int rc = check_profile(prof)) return rc;
+  for (int s = 0; s < n_scen; s++) {
+    if (int rc = check_cluster(&clusters[s])) return rc;
+    if (int rc = validate(&clusters[s], &podsets[s], podsets[s].n_pods)) return rc;
+  }
+  SweepPlan pl;
+  const int rc = sweep_plan(prof, n_scen, clusters, podsets, pl);
+  out[0] = pl.simple ? 1 : 0;
+  out[1] = pl.form ? 1 : 0;
+  out[2] = pl.scen;
+  out[3] = pl.pod;
+  return rc ? rc : pl.code;
+}
+
 const char* kss_plan_reason(int32_t code) { return code >= 0 && code < GP_NCODES ? kGpReason[code] : "unknown"; }
 
 // k_simple_tab with the flat exchange (simple_sync_flat): every wave publishes its own entry,
@@ -5823,4 +5976,43 @@ static const void* spread_pi_fn(bool def, bool lb, bool win) {
   if (def)
     return lb ? (const void*)k_spread<true, false, 256, false, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, false, true>;
   return lb ? (const void*)k_spread<false, false, 256, false, true> : (const void*)k_spread<false, false, KSS_MAX_THREADS, false, true>;
+}
+
+// k_simple's ports-and-images form for a scenario sweep (option sweep_ports_images): k_simple_pi's
+// unrestricted path over many jobs.  sports_all holds every job's NodePorts masks in the order of
+// the sweep's `chosen` array, pod_off[ji] the first of job ji (DevJob does not grow: every kernel
+// copies it).  Both modes occur within one ragged sweep: a 37-node scenario in a 512-lane workgroup
+// runs per wave, a 1,000-node one does not.  No window instantiation (a sweep below 100 % runs on
+// k_schedule).  Defined here, behind every other kernel, so those keep their places in the code object.
+template <bool DEF>
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_pi_sweep(const DevJob* __restrict__ jobs, kss_profile prof, int W,
+                                                                     int cap, int k0, int k1, unsigned long long* gran,
+                                                                     int* err, unsigned long long* stamps, XPeers X,
+                                                                     unsigned epoch0, int stat_row0, int k_find,
+                                                                     const SPort* sports_all, const int32_t* pod_off) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const int Wl = X.n > 1 ? X.wl : W;
+  const int ji = blockIdx.x / Wl, w = X.w_off + (int)(blockIdx.x % Wl);
+  const DevJob job = jobs[ji];
+  constexpr kss_profile def_prof = default_profile_c();
+  if (!DEF) stage_profile(H, jobs[ji].prof);
+  const kss_profile& P = DEF ? def_prof : H.prof;
+  const int per = (job.c.N + W - 1) / W, nwave = (int)(blockDim.x >> 6);
+  unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
+  unsigned long long* sp = ji == 0 ? stamps : nullptr;
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  const SPort* sports = sports_all + pod_off[ji];
+  if (per <= PW_LANES * nwave)
+    simple_schedule<DEF, true, false, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                            job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                            sports);
+  else
+    simple_schedule<DEF, false, false, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                             job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                             sports);
+}
+
+static const void* simple_pi_sweep_fn(bool def) {
+  return def ? (const void*)k_simple_pi_sweep<true> : (const void*)k_simple_pi_sweep<false>;
 }

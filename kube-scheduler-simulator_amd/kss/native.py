@@ -71,7 +71,9 @@ SIGNATURES = [
     ("kss_sweep_create", C.c_void_p, [C.c_int32, P(abi.Profile), C.c_int32, P(abi.Cluster), P(abi.PodSet)]),
     ("kss_sweep_run", C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_double)]),
     ("kss_sweep_info", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_int32), P(C.c_int64)]),
+    ("kss_sweep_form", C.c_int, [C.c_void_p]),
     ("kss_sweep_destroy", None, [C.c_void_p]),
+    ("kss_plan_sweep", C.c_int, [P(abi.Profile), C.c_int32, P(abi.Cluster), P(abi.PodSet), P(C.c_int32)]),
     ("kss_last_timing", C.c_int, [C.c_void_p, P(C.c_double), P(C.c_int32)]),
     ("kss_last_loop_timing", C.c_int, [C.c_void_p, P(C.c_double)]),
     ("kss_last_handoff_retries", C.c_int, [C.c_void_p, P(C.c_int32)]),
@@ -794,7 +796,11 @@ class Sweep:
     def info(self):
         ms, k, b = C.c_double(0), C.c_int32(0), C.c_int64(0)
         check(lib().kss_sweep_info(self.h, C.byref(ms), C.byref(k), C.byref(b)))
-        return {"stage_ms": ms.value, "kernel": "k_simple" if k.value == 1 else "k_schedule", "upload_bytes": b.value}
+        form = lib().kss_sweep_form(self.h)
+        if form < 0:
+            check(form)
+        return {"stage_ms": ms.value, "kernel": "k_simple" if k.value == 1 else "k_schedule", "upload_bytes": b.value,
+                "ports_images": bool(form)}
 
     def close(self):
         if getattr(self, "h", None):
@@ -848,3 +854,21 @@ def plan_service(cluster: abi.Cluster, podset: abi.PodSet, profile: Optional[abi
     out = (C.c_int32 * 3)()
     check(lib().kss_plan_service(C.byref(cluster), C.byref(podset), C.byref(profile) if profile is not None else None, out))
     return {"chain": int(out[0]), "pod": int(out[1]), "reason": lib().kss_plan_reason(out[2]).decode()}
+
+
+def plan_sweep(profile: abi.Profile, clusters: List[abi.Cluster], podsets: List[abi.PodSet]) -> dict:
+    """Host-only: the routing kss_sweep_create would choose for these scenarios (kss_plan_sweep; the
+    same function decides both): the kernel of the whole sweep, whether it runs in the
+    ports-and-images form, and the first scenario and pod that keep it off the k_simple family (-1:
+    none, or no single one) with the reason.  Follows the option sweep_ports_images; raises KssError
+    (-95) exactly where Sweep(...) would: a pod with a volume program, or with the option 0 a pod with
+    host ports or node-cached images."""
+    n = len(clusters)
+    carr = (abi.Cluster * max(n, 1))(*clusters)
+    parr = (abi.PodSet * max(n, 1))(*podsets)
+    out = (C.c_int32 * 4)()
+    rc = lib().kss_plan_sweep(C.byref(profile), n, carr, parr, out)
+    if rc < 0:
+        check(rc)
+    return {"kernel": "k_simple" if out[0] == 1 else "k_schedule", "form": bool(out[1]), "scenario": int(out[2]),
+            "pod": int(out[3]), "reason": lib().kss_plan_reason(rc).decode()}
