@@ -481,7 +481,16 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * which kernel a staged batch runs on does not follow it; kss_plan_service follows it),
  * "sweep_ports_images" (default 0, independent of the four above; 1: a scenario sweep whose pods
  * hold host ports or node-cached images is staged instead of refused -- see kss_sweep_create;
- * a sweep without such a pod is staged and launched as with 0; kss_plan_sweep follows it).  Read when a context is created (shards, xcd, xcd_shards,
+ * a sweep without such a pod is staged and launched as with 0; kss_plan_sweep follows it),
+ * "simple_volumes" (default 0; effective only with "simple_ports_images" 1: a staged, unrecorded
+ * batch that meets that form's conditions and holds a pod with a volume program runs on k_simple's
+ * volumes form, kss_last_simple_form, instead of k_schedule -- on one part, chunked launches and
+ * runtime profiles included -- provided no pod has a WaitForFirstConsumer claim
+ * (KSS_VOL_BIND_WFFC), the cluster has at most 64 volume rows and 8 attach-limit keys, every shared
+ * KSS_VOL_LIMIT entry names its row's key, and per key the largest attached count plus everything
+ * the batch can add, and every limit, stay below 65535; a batch under percentageOfNodesToScore <
+ * 100, the shape table, k_spread, sweeps, split grids and the service grid do not take such pods;
+ * a batch without a volume program is routed and launched as with 0; kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -883,6 +892,11 @@ int kss_last_shape_table(kss_ctx* ctx, int32_t* out2);
  * by a shape-table batch on two or more shards of one part (not a split grid) with at most 128
  * entries.  Option "flat_exchange": 1 (default) where admitted, 0 the two-level form. */
 int kss_last_simple_exchange(kss_ctx* ctx, int32_t* out2);
+/* The form of k_simple the last run took: out2[0] = 1 when it ran the volumes form (option
+ * "simple_volumes": pods with volume programs; the volume filters on a used-rows word and packed
+ * attach counters per node in LDS), else 0; out2[1] = the loop kernel's dynamic LDS bytes per
+ * workgroup (0 when the last run was not on k_simple).  kss_last_kernel stays 1. */
+int kss_last_simple_form(kss_ctx* ctx, int32_t* out2);
 /* kernel of the last scheduling launch: 0 general (k_schedule), 1 compact (k_simple:
  * batches without spread / inter-pod programs and without a record), 2 k_spread (batches
  * with programs, without a record), 3 k_preempt (kss_postfilter_pod); <0 on error */

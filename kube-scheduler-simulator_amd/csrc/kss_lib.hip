@@ -27,6 +27,10 @@
 //   k_simple_tab_pi, k_simple_tab_flat_pi  the two table kernels for an image-only batch of the
 //                ports-and-images form: k_static_pi's words, ImageLocality added to the key
 //                (options simple_ports_images and table_images; no pod holds a host port).
+//   k_simple_vol  k_simple's volumes form (options simple_ports_images and simple_volumes): pods
+//                with volume programs; a used-rows word and packed attach counters per node in
+//                LDS, VolumeBinding / VolumeZone in the static word (k_static_vol), the columns
+//                packed / written back around the batch (k_vol_pack, k_vol_unpack, k_vol_counts).
 //   k_spread    the sequential loop of batches WITH spread / inter-pod-affinity programs
 //                (no result record): node rows, label ids, the pod's count rows and
 //                the launch's commits in LDS, host-resolved pod programs (GPod),
@@ -82,7 +86,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_SIMPLE_VOL, O_N
 };
 struct OptDef {
   const char* name;
@@ -125,6 +129,7 @@ const OptDef kOptDefs[O_N] = {
     {"spread_ports_images", "KSS_SPREAD_PORTS_IMAGES", 0},  // k_spread's ports-and-images form (independent of simple_ports_images)
     {"service_ports_images", "KSS_SERVICE_PORTS_IMAGES", 0},  // the service grid's k_simple-shaped chain for such pods (independent of the three above)
     {"sweep_ports_images", "KSS_SWEEP_PORTS_IMAGES", 0},  // scenario sweeps admit such pods: k_simple_pi_sweep or k_schedule (independent of the four above)
+    {"simple_volumes", "KSS_SIMPLE_VOLUMES", 0},  // k_simple's volumes form for pods with volume programs (effective only with simple_ports_images 1)
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -498,6 +503,27 @@ __global__ void k_handoff_final_pi(const DevJob* __restrict__ jobs, int W, int w
 static const void* spread_pi_fn(bool def, bool lb, bool win);
 // ... and k_simple_pi_sweep<DEF>, the ports-and-images form of a scenario sweep, behind those
 static const void* simple_pi_sweep_fn(bool def);
+// ... and the volumes form of k_simple (option simple_volumes), behind those: k_simple_vol<DEF>, the
+// static verdicts (k_static_vol) and the node-state columns' pack / write-back kernels
+static const void* simple_vol_fn(bool def);
+static void launch_static_vol(hipStream_t st, const DevJob* jobs, const kss_profile& pr, int k0, int k1, int n_lo, int n_hi,
+                              const SVolLaunch* vl);
+static void launch_vol_writeback(hipStream_t st, const DevJob* jobs, int n_nodes, int n_pods, const SVolLaunch* vl);
+static int vol_pack_state(kss_ctx* ctx, bool& fits);
+// The form's launch block on the device (kss_ctx::vol_state_buf): SVolLaunch, the maxima k_vol_pack
+// reports, then the used / attached / limit columns of N nodes.
+struct VolStateLayout {
+  size_t o_chk, o_used, o_att, o_lim, bytes;
+  explicit VolStateLayout(size_t N) {
+    o_chk = 256;
+    o_used = 512;
+    o_att = o_used + 8 * N;
+    o_lim = o_att + 16 * N;
+    bytes = o_lim + 16 * N;
+  }
+};
+static_assert(sizeof(SVolLaunch) <= 256, "the launch block's first 256 bytes");
+__global__ void k_vol_pack(DevCluster c, uint64_t* used, uint64_t* att, uint64_t* lim, int32_t* chk);
 
 // Static words of pods [k0, min(k1, n_pods)) x every node of every job.  grid: x = 1024-node
 // tiles, y = groups of STATIC_PODS pods, z = job.  One lane per QUAD of adjacent nodes walks its
@@ -972,6 +998,16 @@ struct kss_ctx {
   bool spod_ports = false;  // ... and some pod of it holds a host port (no shape table: UsedPorts is loop state)
   DevBuf sport_buf;
   std::vector<SPort> sport_host;
+  // its volumes form (option simple_volumes): the staged batch holds a pod with a volume program
+  // and vol_form_admit took it (k_simple_vol, one part, no window); the pods' SVol records, what
+  // their commits can add per limit key (condition 4 is checked at run time against the device's
+  // columns), and the launch's block: SVolLaunch, the packed node-state columns, the maxima
+  bool spod_vol = false;
+  DevBuf svol_buf, vol_state_buf;
+  std::vector<SVol> svol_host;
+  uint64_t spod_vol_add[SV_KEYS] = {};
+  std::vector<int32_t> vol_row_key_h, vol_key_plugin_h;  // host copies (load)
+  int last_simple_form[2] = {0, 0};  // the last run: the volumes form used, the loop kernel's LDS bytes
   bool staged_names = false;  // some staged pod has a NodeAffinity PreFilterResult node list
   // host-resolved programs of the staged pods for k_spread (gpod_ok false: k_schedule)
   DevBuf gpod_buf;
@@ -1310,8 +1346,9 @@ bool pod_ports_images(const kss_pod& p) { return (p.port_conflict | p.port_add) 
 // Compact record of one pod (kss_simple.cuh SPod); false when the preferred NodeAffinity
 // weights do not fit the static word's 20 bits.  pi: a record of the ports-and-images form, which
 // admits NodePorts / ImageLocality pods and whose static word holds 13 bits of NodeAffinity.
-bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, bool pi = false) {
-  if ((!pi && pod_ports_images(p)) || p.vol_len > 0) return false;  // NodePorts / ImageLocality / volumes: k_schedule
+// vol: ... of its volumes form (option simple_volumes; the caller ran vol_form_admit), which admits volume programs.
+bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, bool pi = false, bool vol = false) {
+  if ((!pi && pod_ports_images(p)) || (!vol && p.vol_len > 0)) return false;  // NodePorts / ImageLocality / volumes: k_schedule
   int64_t wsum = 0;
   for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
   if (wsum > (pi ? (int64_t)SWPI_NA_MAX : 0xFFFFF)) return false;  // static word: 20 (13) bits of raw NodeAffinity
@@ -1350,30 +1387,62 @@ struct PiRecords {
   bool form = false;
   int na_pod = -1;
   std::vector<SPort> ports;
+  // the volumes form (option simple_volumes, a variant of that form; build_spods' `va`): some pod
+  // has a volume program and vol_form_admit took the batch (vol; vols: the pods' SVol records,
+  // vol_add: what their commits can add per limit key), or refused it (vol_code: the GP_VOL_*
+  // reason, vol_pod: the pod it names)
+  bool vol = false;
+  int vol_code = 0, vol_pod = -1;
+  std::vector<SVol> vols;
+  uint64_t vol_add[SV_KEYS] = {};
 };
+
+// What the volumes form's admission reads of the cluster.  att_max / lim_max: per key, the largest
+// vol_attached / vol_limit over the nodes (null: condition 4 is checked later, vol_fields_fit --
+// run_single reads the maxima of the device's current columns).
+struct VolAdmit {
+  int n_rows = 0, n_keys = 0;
+  const int32_t* row_key = nullptr;
+  const int32_t* att_max = nullptr;
+  const int32_t* lim_max = nullptr;
+};
+
+int vol_fields_fit(const uint64_t (&add)[SV_KEYS], const int32_t* att_max, const int32_t* lim_max, int n_keys);
+bool vol_form_admit(const kss_podset* ps, const VolAdmit& A, PiRecords& out);
 // svc (staging only): the option service_ports_images asks for that form as well -- the service
 // grid reads the staged records; which kernel a staged batch runs on still follows
 // simple_ports_images alone (run_single).
 // force (a scenario of a sweep in that form, sweep_plan): records of the form whatever the options
 // and the pods say -- one launch serves every scenario, so a scenario without such a pod gets them
 // too, with zero masks.
+// va (the callers that can route a batch to k_simple_vol: kss_plan_podset, stage_spods): with the
+// options simple_ports_images and simple_volumes both on, a batch that holds a pod with a volume
+// program is put to vol_form_admit; admitted, it gets records of the ports-and-images form (whether
+// or not a pod has ports or images) and pi->vols, and no shapes (no table for it).  Refused, or
+// without va, or without such a pod, the batch is built exactly as before.
 bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr,
-                 PiRecords* pi = nullptr, bool svc = false, bool force = false) {
+                 PiRecords* pi = nullptr, bool svc = false, bool force = false, const VolAdmit* va = nullptr) {
   out.assign((size_t)std::max(ps->n_pods, 1), SPod{});
   if (n_shapes) *n_shapes = 0;
-  bool form = false;
+  bool form = false, vol = false;
   if (pi) {
     *pi = PiRecords{};
     form = force;
     if (opt(O_SIMPLE_PI) || (svc && opt(O_SERVICE_PI)))
       for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
+    if (va && !force && opt(O_SIMPLE_PI) && opt(O_SIMPLE_VOL)) {
+      bool any = false;
+      for (int i = 0; i < ps->n_pods; i++) any |= ps->pods[i].vol_len > 0;
+      vol = any && vol_form_admit(ps, *va, *pi);
+      form |= vol;
+    }
     pi->form = form;
     if (form) pi->ports.assign((size_t)std::max(ps->n_pods, 1), SPort{});
   }
   for (int i = 0; i < ps->n_pods; i++) {
     const kss_pod& p = ps->pods[i];
     if (p.n_hard | p.n_soft | p.ipa_len) return false;
-    if (!fill_spod(ps, p, n_scalar, out[(size_t)i], form)) {
+    if (!fill_spod(ps, p, n_scalar, out[(size_t)i], form, vol)) {
       if (form && p.vol_len == 0) {  // the form's own limit: weights the 20-bit field would hold
         int64_t wsum = 0;
         for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
@@ -1395,7 +1464,7 @@ bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int
     out[(size_t)i].shape = ids[(size_t)i];
     out[(size_t)i].shape_rep = rep[(size_t)i];
   }
-  if (n_shapes) *n_shapes = ns;
+  if (n_shapes) *n_shapes = vol ? 0 : ns;  // (the volumes form takes no shape table)
   return true;
 }
 
@@ -1435,7 +1504,13 @@ enum {
   GP_SWEEP_PCT,
   GP_SWEEP_VALUES,
   GP_SWEEP_GEOMETRY,
-  GP_NCODES
+  GP_VOL_WFFC,
+  GP_VOL_ROWS,
+  GP_VOL_KEYS,
+  GP_VOL_ROW_KEY,
+  GP_VOL_PCT,
+  GP_VOL_FIELD0,  // + the key, 0 .. SV_KEYS - 1
+  GP_NCODES = GP_VOL_FIELD0 + SV_KEYS
 };
 const char* const kGpReason[GP_NCODES] = {
     "eligible",
@@ -1472,7 +1547,118 @@ const char* const kGpReason[GP_NCODES] = {
     "percentageOfNodesToScore below 100: the whole sweep runs on k_schedule",
     "a scenario's values or the profile's weights leave the exact f64 envelope: the whole sweep runs on k_schedule",
     "the option no_simple, or the largest scenario does not fit one workgroup's LDS: the whole sweep runs on k_schedule",
+    "a WaitForFirstConsumer claim (the binder's assume cache is global state that crosses shards): k_simple's volumes "
+    "form does not take it, k_schedule only",
+    "more than 64 volume rows (k_simple's volumes form keeps a node's used rows in one 64-bit word): k_schedule only",
+    "more than 8 attach-limit keys (k_simple's volumes form packs 8 counters per node): k_schedule only",
+    "a volume program k_simple's volumes form cannot restate (a shared volume listed under another limit key than "
+    "its row's, or one key's entries in two runs): k_schedule only",
+    "percentageOfNodesToScore below 100 with a volume program (k_simple's volumes form has no window variant): "
+    "k_schedule only",
+#define KSS_VOL_FIELD_REASON(k)                                                                                       \
+  "attach-limit key " #k ": the attached count the batch can reach, or a node's limit, exceeds 65534 (k_simple's " \
+  "volumes form packs 16-bit counters): k_schedule only"
+    KSS_VOL_FIELD_REASON(0), KSS_VOL_FIELD_REASON(1), KSS_VOL_FIELD_REASON(2), KSS_VOL_FIELD_REASON(3),
+    KSS_VOL_FIELD_REASON(4), KSS_VOL_FIELD_REASON(5), KSS_VOL_FIELD_REASON(6), KSS_VOL_FIELD_REASON(7),
+#undef KSS_VOL_FIELD_REASON
 };
+static_assert(SV_KEYS == 8, "one reason text per key");
+
+// The packed fields cannot overflow: per key, the largest attached count plus everything the
+// batch's pods can add under the key, and every limit, fit a field.  The first failing key, or -1.
+int vol_fields_fit(const uint64_t (&add)[SV_KEYS], const int32_t* att_max, const int32_t* lim_max, int n_keys) {
+  for (int k = 0; k < n_keys && k < SV_KEYS; k++)
+    if ((uint64_t)std::max(att_max[k], 0) + add[k] > SV_FIELD_MAX || lim_max[k] > (int32_t)SV_FIELD_MAX) return k;
+  return -1;
+}
+
+// The one admission decision of k_simple's volumes form, shared by kss_plan_podset and stage_spods /
+// run_single: a (validated) batch whose pods' volume programs the form restates exactly.  Fills the
+// pods' records and the per-key adds; on refusal the reason code and the first offending pod.
+bool vol_form_admit(const kss_podset* ps, const VolAdmit& A, PiRecords& out) {
+  auto refuse = [&](int code, int pod) {
+    out.vol_code = code;
+    out.vol_pod = pod;
+    return false;
+  };
+  int first = -1;
+  for (int i = 0; i < ps->n_pods; i++) {
+    const kss_pod& p = ps->pods[i];
+    if (p.vol_len > 0 && first < 0) first = i;
+    for (int e = 0; e < p.vol_len; e++)
+      if (ps->vols[p.vol_off + e].kind == KSS_VOL_BIND_WFFC) return refuse(GP_VOL_WFFC, i);
+  }
+  if (A.n_rows > SV_ROWS) return refuse(GP_VOL_ROWS, first);
+  if (A.n_keys > SV_KEYS) return refuse(GP_VOL_KEYS, first);
+  out.vols.assign((size_t)std::max(ps->n_pods, 1), SVol{});
+  for (int k = 0; k < SV_KEYS; k++) out.vol_add[k] = 0;
+  for (int i = 0; i < ps->n_pods; i++) {
+    const kss_pod& p = ps->pods[i];
+    SVol& r = out.vols[(size_t)i];
+    uint64_t pnew[SV_KEYS] = {}, padd[SV_KEYS] = {};
+    int cur = -1;         // the limit key of the open run of KSS_VOL_LIMIT entries
+    uint32_t closed = 0;  // keys whose run ended: filter_volumes_t checks a run by itself
+    for (int e = 0; e < p.vol_len; e++) {
+      const kss_vol& v = ps->vols[p.vol_off + e];
+      if (v.kind != KSS_VOL_LIMIT && cur >= 0) {
+        closed |= 1u << cur;
+        cur = -1;
+      }
+      switch (v.kind) {
+        case KSS_VOL_CONFLICT:
+          r.conflict |= 1ull << v.row;
+          break;
+        case KSS_VOL_LIMIT:
+          if (v.key != cur) {
+            if (cur >= 0) closed |= 1u << cur;
+            if ((closed >> v.key) & 1u) return refuse(GP_VOL_ROW_KEY, i);
+            cur = v.key;
+          }
+          r.keys |= 1u << v.key;
+          if (v.row >= 0) {
+            if (A.row_key[v.row] != v.key) return refuse(GP_VOL_ROW_KEY, i);
+            r.shared |= 1ull << v.row;
+          } else {
+            pnew[v.key] += (uint64_t)v.count;
+          }
+          break;
+        case KSS_VOL_BIND_AFFINITY:
+        case KSS_VOL_BIND_PV_MISSING:
+        case KSS_VOL_ZONE:
+        case KSS_VOL_ZONE_ERROR:
+          r.keys |= SV_STATIC;
+          break;
+        case KSS_VOL_OWN: {
+          const int rk = A.row_key[v.row];
+          if (rk >= 0 && !((r.own >> v.row) & 1ull)) {
+            r.keys |= 1u << (16 + rk);
+            out.vol_add[rk] += 1;
+          }
+          r.own |= 1ull << v.row;
+          break;
+        }
+        case KSS_VOL_OWN_PRIVATE:
+          padd[v.key] += (uint64_t)v.count;
+          r.keys |= 1u << (16 + v.key);
+          out.vol_add[v.key] += (uint64_t)v.count;
+          break;
+        default:
+          break;
+      }
+    }
+    for (int k = 0; k < SV_KEYS; k++) {
+      if (pnew[k] > SV_FIELD_MAX || padd[k] > SV_FIELD_MAX) return refuse(GP_VOL_FIELD0 + k, i);
+      r.pnew[k] = (uint16_t)pnew[k];
+      r.padd[k] = (uint16_t)padd[k];
+    }
+  }
+  if (A.att_max && A.lim_max) {
+    const int k = vol_fields_fit(out.vol_add, A.att_max, A.lim_max, A.n_keys);
+    if (k >= 0) return refuse(GP_VOL_FIELD0 + k, first);
+  }
+  out.vol = true;
+  return true;
+}
 
 bool gfail(GpodNeeds& need, int code, int pod) {
   need.fail_code = code;
@@ -2110,6 +2296,8 @@ void kss_destroy(kss_ctx* ctx) {
   ctx->job_buf.release();
   ctx->spod_buf.release();
   ctx->sport_buf.release();
+  ctx->svol_buf.release();
+  ctx->vol_state_buf.release();
   ctx->stat_buf.release();
   ctx->bound_buf.release();
   ctx->pre_buf.release();
@@ -2203,6 +2391,8 @@ int kss_load_cluster(kss_ctx* ctx, const kss_cluster* cl) {
   ctx->key_card_h.assign(cl->key_card, cl->key_card + cl->n_label_keys);
   ctx->key_flags_h.assign(cl->key_flags, cl->key_flags + cl->n_label_keys);
   ctx->key_empty_h.assign(cl->key_empty, cl->key_empty + cl->n_label_keys);
+  ctx->vol_row_key_h.assign(cl->vol_row_key, cl->vol_row_key + (cl->vol_row_key ? cl->n_vol_rows : 0));
+  ctx->vol_key_plugin_h.assign(cl->vol_key_plugin, cl->vol_key_plugin + (cl->vol_key_plugin ? cl->n_vol_keys : 0));
   {
     double sc = 0, st = 0;
     if (cl->class_count)
@@ -2989,10 +3179,12 @@ static bool same_profile(const kss_profile& a, const kss_profile& b) {
 // re-evaluates the candidate after the previous commit).
 static int simple_cap(const Geometry& g) { return g.npt * g.threads; }
 
-static bool simple_fits(const Geometry& g, int nsc, bool pi = false) {  // pi: k_simple_pi's LDS
+static bool simple_fits(const Geometry& g, int nsc, bool pi = false, bool vol = false) {  // pi: k_simple_pi's LDS; vol: k_simple_vol's
   const int pf_n = g.threads > 64 ? g.threads - 64 : g.threads;  // prefetch lanes (kss_simple.cuh)
   return g.W <= 64 * SX_CHUNKS && g.npt <= KSS_MAX_NPT && (simple_cap(g) + pf_n - 1) / pf_n <= PF_MAX &&
-         (pi ? simple_lds_bytes_pi(simple_cap(g), nsc) : simple_lds_bytes(simple_cap(g), nsc)) <= KSS_LDS_BUDGET;
+         (vol  ? simple_lds_bytes_vol(simple_cap(g), nsc)
+          : pi ? simple_lds_bytes_pi(simple_cap(g), nsc)
+               : simple_lds_bytes(simple_cap(g), nsc)) <= KSS_LDS_BUDGET;
 }
 
 // k_simple's shape table (k_simple_tab) for a batch of n_shapes resource shapes on geometry g:
@@ -3123,7 +3315,13 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
                          hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
                          int n_shapes = 0, bool flat = false, const SPort* sports = nullptr,
-                         const int32_t* pod_off = nullptr) {
+                         const int32_t* pod_off = nullptr, const SVolLaunch* vl = nullptr) {
+  // the volumes form (one job; vl: the launch block on the device, vol_pack_state): k_static_pi +
+  // k_static_vol + k_simple_vol per chunk, then the packed attached counts back into vol_attached
+  // and the pods' own rows into vol_count (k_vol_unpack, k_vol_counts).  No table, no window, no split.
+  const bool vol = vl != nullptr;
+  if (vol && (!sports || pod_off || n_shapes > 0 || k_find > 0 || split || n_jobs != 1 || st2))
+    return fail(KSS_E_INVAL, "volumes form: one job of the ports-and-images form, no table, window or split");
   // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
   // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
   const bool pi = sports != nullptr;
@@ -3143,13 +3341,17 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   const bool win = k_find > 0;
   // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
   const bool tab = n_shapes > 0 && def && !win && nsc == 0;
-  const size_t shmem = tab ? simple_lds_bytes(cap, 0, n_shapes) : pi ? simple_lds_bytes_pi(cap, nsc) : simple_lds_bytes(cap, nsc);
+  const size_t shmem = tab   ? simple_lds_bytes(cap, 0, n_shapes)
+                       : vol ? simple_lds_bytes_vol(cap, nsc)
+                       : pi  ? simple_lds_bytes_pi(cap, nsc)
+                             : simple_lds_bytes(cap, nsc);
   // flat: the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
   flat = flat && tab && n_jobs == 1 && !(split && split->X.n > 1);
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
   if (flat && gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
     return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
   const void* fn = pi_sweep ? simple_pi_sweep_fn(def)
+                   : vol   ? simple_vol_fn(def)
                    : flat  ? (pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat)
                    : tab ? (pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab)
                    : pi  ? (win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
@@ -3197,6 +3399,10 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     } else {
       launch_static(st, def, jobs, pr, n_jobs, k0, k1, n_lo, n_hi, max_keys, 0, pi);
       HIP_TRY(hipGetLastError());
+      if (vol) {  // VolumeBinding / VolumeZone verdicts into the words just written
+        launch_static_vol(st, jobs, pr, k0, k1, n_lo, n_hi, vl);
+        HIP_TRY(hipGetLastError());
+      }
     }
     unsigned epoch0 = 0;
     unsigned long long* gc = gran;
@@ -3209,7 +3415,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     unsigned long long* sp = k0 == 0 ? stamps : nullptr;
     void* args[] = {(void*)&jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
                     (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg,
-                    (void*)&sports, (void*)&pod_off};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's two; the other kernels take 13)
+                    (void*)&sports, vol ? (void*)&vl : (void*)&pod_off};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's / k_simple_vol's two; the other kernels take 13)
     const int ci = k0 / chunk;
     if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
     if (xcd) {
@@ -3237,6 +3443,10 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   hipLaunchKernelGGL(k_counts, dim3((unsigned)((n_pods_max + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, jobs, 0,
                      n_pods_max);
   HIP_TRY(hipGetLastError());
+  if (vol) {
+    launch_vol_writeback(st, jobs, max_nodes, n_pods_max, vl);
+    HIP_TRY(hipGetLastError());
+  }
   return 0;
 }
 
@@ -3482,11 +3692,20 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   // k_schedule only
   const bool nomq = !ctx->nom.empty();
   if (nomq && split) return fail(KSS_E_UNSUPPORTED, "split grids do not read the nominator");
-  const bool simple_ok = simple_win_ok && !nomq && staged && ctx->spod_ok && commit && !record && !keep_norm && !need.general &&
-                         scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
-                         !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
-                         // the ports-and-images form: one part, and the option still on (it is process-wide)
-                         (!ctx->spod_pi || (!split && opt(O_SIMPLE_PI)));
+  bool simple_ok = simple_win_ok && !nomq && staged && ctx->spod_ok && commit && !record && !keep_norm && !need.general &&
+                   scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
+                   !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
+                   // the ports-and-images form: one part, and the option still on (it is process-wide)
+                   (!ctx->spod_pi || (!split && opt(O_SIMPLE_PI))) &&
+                   // its volumes form: that option too, and no window (no WIN instantiation)
+                   (!ctx->spod_vol || (opt(O_SIMPLE_VOL) && !(window && k_find < (int)N)));
+  // ... and the packed fields cannot overflow (vol_form_admit's condition 4) on the columns as they
+  // are now: packed here, before the batch's first launch
+  if (simple_ok && ctx->spod_vol) {
+    bool fits = false;
+    if ((rc = vol_pack_state(ctx, fits))) return rc;
+    simple_ok = fits;
+  }
   if (simple_ok && ctx->force_w <= 0 && !split) W = std::min(W, 64 * SX_CHUNKS);
   // XCD-local k_simple (launch_simple xcd, xcd_slot): a cluster whose shards fit one XCD's CUs
   // at one node per lane runs every shard on XCD 0, so the per-pod exchange stays in that
@@ -3529,8 +3748,9 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (split && ctx->split_wl > ctx->n_cu) return fail(KSS_E_UNSUPPORTED, "split grid: more shards per part than CUs");
   Geometry g;
   if (!pick_geometry((int)N, W, ctx->pref_threads, g)) return fail(KSS_E_UNSUPPORTED, "no geometry for this cluster");
-  const bool simple = simple_ok && simple_fits(g, ctx->dc.n_scalar, ctx->spod_pi);
+  const bool simple = simple_ok && simple_fits(g, ctx->dc.n_scalar, ctx->spod_pi, ctx->spod_vol);
   const bool simple_pi = simple && ctx->spod_pi;
+  const bool simple_vol = simple && ctx->spod_vol;
   const int n_res = (int)ctx->gneed.res_rows.size();
   bool spread = spread_ok && spread_fits(g, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar);
   if (spread && !simple && opt(O_THREADS) <= 0 && opt(O_FORCE_THREADS) <= 0) {
@@ -3734,7 +3954,8 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   // the shape table: the whole staged batch (its shape directory sits in its first records)
   // (the ports-and-images form: an image-only batch, option table_images -- k_simple_tab_pi;
   // UsedPorts is not a function of the resource shape, so a host-port pod keeps the batch on k_simple_pi)
-  const bool tab = simple && (!simple_pi || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
+  // (the volumes form: never -- its batches have no shapes)
+  const bool tab = simple && !simple_vol && (!simple_pi || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
                    n == ctx->staged_n &&
                    shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
   ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;
@@ -3742,11 +3963,18 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   const bool flat = tab && flat_exchange_ok(g, (int)N, ctx->prof, split);
   ctx->last_flat[0] = flat ? 1 : 0;
   ctx->last_flat[1] = flat ? g.W * (g.threads / 64) : 0;
+  ctx->last_simple_form[0] = simple_vol ? 1 : 0;
+  ctx->last_simple_form[1] = !simple ? 0
+                             : (int)(tab          ? simple_lds_bytes(simple_cap(g), 0, ctx->spod_shapes)
+                                     : simple_vol ? simple_lds_bytes_vol(simple_cap(g), ctx->dc.n_scalar)
+                                     : simple_pi  ? simple_lds_bytes_pi(simple_cap(g), ctx->dc.n_scalar)
+                                                  : simple_lds_bytes(simple_cap(g), ctx->dc.n_scalar));
   if (simple)
     rc = launch_simple(ctx->stream, g, 1, jd, ctx->prof, n, (int)N, chunk, gran, gb,
                        errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr, ctx->dc.n_scalar, ctx->last_xcd[0] != 0,
                        &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0, flat,
-                       simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr);
+                       simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr, nullptr,
+                       simple_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr);
   else if (spread)
   {
     const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi);
@@ -3861,6 +4089,45 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   return dump_stamps();
 }
 
+// The volumes form before a batch's first launch (run_single; the staged batch is of the form):
+// the node-state columns packed from the device's vol_count / vol_attached / vol_limit as they are
+// now (k_vol_pack), the launch block uploaded, and vol_form_admit's condition 4 on the maxima the
+// pack reports -- one small read-back and one synchronisation, paid by a batch of the form only.
+// fits false: a field could overflow; nothing was changed and the batch runs on k_schedule.
+static int vol_pack_state(kss_ctx* ctx, bool& fits) {
+  const size_t N = (size_t)std::max(ctx->dc.N, 1);
+  const VolStateLayout VL(N);
+  if (int rc = ctx->vol_state_buf.ensure(VL.bytes)) return rc;
+  char* b = (char*)ctx->vol_state_buf.p;
+  SVolLaunch K{};
+  const uint32_t en = ctx->prof.filter_enabled;
+  for (int r = 0; r < ctx->dc.n_vol_rows && r < SV_ROWS; r++) {
+    const int k = ctx->vol_row_key_h[(size_t)r];
+    if (k >= 0 && k < SV_KEYS) K.keyrows[k] |= 1ull << r;
+  }
+  for (int k = 0; k < ctx->dc.n_vol_keys && k < SV_KEYS; k++) {
+    const int pl = ctx->vol_key_plugin_h[(size_t)k];
+    if ((en >> pl) & 1u) K.key_on |= 1u << k;
+    if (pl == KSS_F_NODE_VOLUME_LIMITS) K.key_csi |= 1u << k;
+  }
+  K.vr_on = (en >> KSS_F_VOLUME_RESTRICTIONS) & 1u;
+  K.used = (uint64_t*)(b + VL.o_used);
+  K.att = (uint64_t*)(b + VL.o_att);
+  K.lim = (uint64_t*)(b + VL.o_lim);
+  K.svols = (const SVol*)ctx->svol_buf.p;
+  int32_t chk[2 * SV_KEYS];
+  for (int i = 0; i < 2 * SV_KEYS; i++) chk[i] = INT32_MIN;
+  HIP_TRY(hipMemcpyAsync(b, &K, sizeof(K), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(b + VL.o_chk, chk, sizeof(chk), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_vol_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dc, K.used, K.att, K.lim,
+                     (int32_t*)(b + VL.o_chk));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(chk, b + VL.o_chk, sizeof(chk), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  fits = vol_fields_fit(ctx->spod_vol_add, chk, chk + SV_KEYS, ctx->dc.n_vol_keys) < 0;
+  return 0;
+}
+
 // compact records (k_simple) or resolved programs (k_spread) of the staged podset (host copy
 // kept alive for the async upload)
 static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
@@ -3873,8 +4140,16 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
     ctx->staged_names |= ps->pods[i].names_len >= 0;
   }
   PiRecords pi;
-  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi, /*svc=*/true);
+  VolAdmit va;  // (condition 4 waits for the run: the columns it reads are the device's)
+  va.n_rows = ctx->dc.n_vol_rows;
+  va.n_keys = ctx->dc.n_vol_keys;
+  va.row_key = ctx->vol_row_key_h.data();
+  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi, /*svc=*/true, false,
+                             (int)ctx->vol_row_key_h.size() == va.n_rows ? &va : nullptr);
   ctx->spod_pi = ctx->spod_ok && pi.form;
+  ctx->spod_vol = ctx->spod_ok && pi.vol;
+  ctx->svol_host.swap(pi.vols);
+  for (int k = 0; k < SV_KEYS; k++) ctx->spod_vol_add[k] = pi.vol_add[k];
   ctx->spod_ports = false;
   for (const SPort& q : pi.ports) ctx->spod_ports |= (q.conflict | q.add) != 0;
   ctx->sport_host.swap(pi.ports);
@@ -3901,6 +4176,11 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   if (ctx->spod_pi) {
     if ((rc = ctx->sport_buf.ensure(sizeof(SPort) * ctx->sport_host.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->sport_buf.p, ctx->sport_host.data(), sizeof(SPort) * ctx->sport_host.size(),
+                           hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (ctx->spod_vol) {
+    if ((rc = ctx->svol_buf.ensure(sizeof(SVol) * ctx->svol_host.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->svol_buf.p, ctx->svol_host.data(), sizeof(SVol) * ctx->svol_host.size(),
                            hipMemcpyHostToDevice, ctx->stream));
   }
   return 0;
@@ -4475,7 +4755,8 @@ static int svc_start_locked(kss_ctx* ctx) {
   // the general chain, for comparison.  On an XCD-local grid when its shards fit one XCD's CUs.
   // A staged list of the ports-and-images form (spod_pi) takes it only with the option
   // service_ports_images on, the static-word table and room for the UsedPorts column (below).
-  const bool simple_pre = ctx->spod_ok && (!ctx->spod_pi || opt(O_SERVICE_PI)) && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
+  // (a staged list of the volumes form, spod_vol, never: that chain takes no volume program)
+  const bool simple_pre = ctx->spod_ok && !ctx->spod_vol && (!ctx->spod_pi || opt(O_SERVICE_PI)) && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
                           f64_exact(ctx->f64_cluster, ctx->f64_pods, ctx->staged_n) && !opt(O_SERVICE_GENERAL);
   const int xcd_cus = ctx->n_cu / XCD_GRID_MULT;
   // (off by default: the record's stores to host memory from one XCD were slower than the L2
@@ -4930,6 +5211,13 @@ int kss_last_simple_exchange(kss_ctx* ctx, int32_t* out2) {
   if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
   out2[0] = ctx->last_flat[0];
   out2[1] = ctx->last_flat[1];
+  return 0;
+}
+
+int kss_last_simple_form(kss_ctx* ctx, int32_t* out2) {
+  if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
+  out2[0] = ctx->last_simple_form[0];
+  out2[1] = ctx->last_simple_form[1];
   return 0;
 }
 
@@ -5796,8 +6084,22 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   out3[0] = 0;
   out3[1] = -1;
   out3[2] = GP_OK;
-  PiRecords pi;  // (follows the process-wide option simple_ports_images)
-  if (build_spods(ps, cl->n_scalar, sp, nullptr, &pi)) {
+  PiRecords pi;  // (follows the process-wide options simple_ports_images and simple_volumes)
+  // the volumes form's admission on the cluster as given (run_single reads the device's columns)
+  const size_t N = (size_t)std::max(cl->n_nodes, 0);
+  std::vector<int32_t> att_max((size_t)std::max(cl->n_vol_keys, 1), 0), lim_max((size_t)std::max(cl->n_vol_keys, 1), -1);
+  for (int k = 0; k < cl->n_vol_keys; k++)
+    for (size_t n = 0; n < N; n++) {
+      att_max[(size_t)k] = std::max(att_max[(size_t)k], cl->vol_attached[(size_t)k * N + n]);
+      lim_max[(size_t)k] = std::max(lim_max[(size_t)k], cl->vol_limit[(size_t)k * N + n]);
+    }
+  VolAdmit va;
+  va.n_rows = cl->n_vol_rows;
+  va.n_keys = cl->n_vol_keys;
+  va.row_key = cl->vol_row_key;
+  va.att_max = att_max.data();
+  va.lim_max = lim_max.data();
+  if (build_spods(ps, cl->n_scalar, sp, nullptr, &pi, false, false, &va)) {
     out3[0] = 1;
     return 0;
   }
@@ -5812,6 +6114,10 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   if (pi.form && pi.na_pod >= 0 && need.fail_code == GP_PORTS_IMAGES) {  // the form's own limit kept it off k_simple
     out3[1] = pi.na_pod;
     out3[2] = GP_PI_NA_WEIGHTS;
+  }
+  if (pi.vol_code != GP_OK && need.fail_code == GP_PORTS_IMAGES) {  // the volumes form refused the batch: its reason
+    out3[1] = pi.vol_pod;
+    out3[2] = pi.vol_code;
   }
   return 0;
 }
@@ -5829,7 +6135,14 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
     if (ps->pods[i].names_len >= 0) names_pod = i;
   const bool win = num_feasible_to_find(cl->n_nodes, prof->pct_nodes_to_score) < cl->n_nodes;
   const bool spread_def = out3[0] == 2 && same_profile(*prof, default_profile_c()) && !opt(O_FOLD);
-  if (win && ((out3[0] == 2 && !spread_def) || names_pod >= 0)) {
+  int vol_pod = -1;  // k_simple's volumes form (the plan above admitted the batch to it) has no window variant
+  for (int i = 0; i < ps->n_pods && vol_pod < 0 && out3[0] == 1; i++)
+    if (ps->pods[i].vol_len > 0) vol_pod = i;
+  if (win && vol_pod >= 0) {
+    out3[0] = 0;
+    out3[1] = vol_pod;
+    out3[2] = GP_VOL_PCT;
+  } else if (win && ((out3[0] == 2 && !spread_def) || names_pod >= 0)) {
     out3[1] = names_pod >= 0 ? names_pod : (ps->n_pods > 0 ? 0 : -1);
     out3[0] = 0;
     out3[2] = GP_PCT;
@@ -6015,4 +6328,161 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_pi_sweep(const DevJo
 
 static const void* simple_pi_sweep_fn(bool def) {
   return def ? (const void*)k_simple_pi_sweep<true> : (const void*)k_simple_pi_sweep<false>;
+}
+
+// ---------------------------------------------------------------------------
+// k_simple's volumes form (option simple_volumes, with simple_ports_images): kss_simple.cuh SVol.
+// Defined here, behind every other kernel, so those keep their places in the code object.
+// ---------------------------------------------------------------------------
+// The loop kernel: k_simple_pi's body (no window instantiation: a windowed batch with a volume
+// program stays on k_schedule) with the launch block `vl` as one more trailing argument.
+template <bool DEF>
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_vol(const DevJob* __restrict__ jobs, kss_profile prof, int W,
+                                                                int cap, int k0, int k1, unsigned long long* gran, int* err,
+                                                                unsigned long long* stamps, XPeers X, unsigned epoch0,
+                                                                int stat_row0, int k_find, const SPort* sports,
+                                                                const SVolLaunch* vl) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const int Wl = X.n > 1 ? X.wl : W;
+  int xs = 0;  // as k_simple
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return 2 * (size_t)W * SX_VALS; }, W, err)) < 0) return;
+  const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
+  const DevJob job = jobs[ji];
+  constexpr kss_profile def_prof = default_profile_c();
+  if (!DEF) stage_profile(H, jobs[ji].prof);
+  const kss_profile& P = DEF ? def_prof : H.prof;
+  const int per = (job.c.N + W - 1) / W, nwave = (int)(blockDim.x >> 6);
+  unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
+  unsigned long long* sp = ji == 0 ? stamps : nullptr;
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  if (per <= PW_LANES * nwave)
+    simple_schedule<DEF, true, false, true, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                                  job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                                  sports, vl);
+  else
+    simple_schedule<DEF, false, false, true, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                                   job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                                   sports, vl);
+}
+
+static const void* simple_vol_fn(bool def) { return def ? (const void*)k_simple_vol<true> : (const void*)k_simple_vol<false>; }
+
+// The static part: the volume filters that no commit changes, over the words k_static_pi just wrote
+// for pods [k0, k1) x rows [n_lo, n_hi) of the one job.  A node whose word passed (verdict 0) and
+// that fails the pod's VolumeBinding bound-claim checks (binder.go checkBoundClaims: a missing PV, or
+// a PV whose node affinity matches no term) or VolumeZone (on zone-labelled nodes: a requirement
+// that does not match, or a per-volume error) gets verdict code 5 -- free in the static word; an
+// unrecorded loop reads only that a node is infeasible -- with the TaintToleration / NodeAffinity /
+// ImageLocality fields zero and the policy bits 3-4 as they were.  The walk is filter_volumes_t's
+// (kss_eval.cuh) restricted to those entries: CONFLICT / LIMIT entries are the loop's, OWN entries end it.
+// grid: x = 256 nodes, y = STATIC_PODS pods.
+constexpr uint32_t SW_VOLUME_STATIC = 5;
+__global__ __launch_bounds__(256) void k_static_vol(const DevJob* __restrict__ jobs, kss_profile prof, int k0, int k1, int n_lo,
+                                                    int n_hi, const SVolLaunch* vl) {
+  const DevJob& job = jobs[0];
+  const DevCluster& c = job.c;
+  const size_t N = (size_t)c.N;
+  const int n = n_lo + (int)(blockIdx.x * 256 + threadIdx.x);
+  const int kend = min(k1, job.n_pods), lim = min(c.N, n_hi);
+  const bool vb = (prof.filter_enabled >> KSS_F_VOLUME_BINDING) & 1u, vz = (prof.filter_enabled >> KSS_F_VOLUME_ZONE) & 1u;
+  if (n >= lim) return;
+  const bool zoned = (node_flags_of(c, n) & KSS_NODE_VOLUME_ZONE) != 0;
+  auto lab = [&](int key) { return label_of(c, key, n); };
+  for (int t = 0; t < STATIC_PODS; t++) {
+    const int k = k0 + (int)blockIdx.y * STATIC_PODS + t;
+    if (k >= kend) break;
+    if (!(vl->svols[k].keys & SV_STATIC)) continue;  // (wave-uniform)
+    uint32_t* wp = &job.stat[(size_t)(k - k0) * N + n];
+    const uint32_t w = ld_ag(wp);
+    if ((w & 7u) != 0) continue;
+    const kss_pod& p = job.P.pods[k];
+    bool bad = false;
+    for (int e = 0; e < p.vol_len && !bad; e++) {
+      const kss_vol& v = job.P.vols[p.vol_off + e];
+      if (v.kind == KSS_VOL_OWN || v.kind == KSS_VOL_OWN_PRIVATE) break;
+      if (v.kind == KSS_VOL_BIND_PV_MISSING) {
+        bad = vb;
+      } else if (v.kind == KSS_VOL_BIND_AFFINITY) {
+        bool ok = false;
+        for (int j = 0; j < v.b && !ok; j++) ok = term_match_t(c, job.P.reqs, job.P.ints, job.P.terms[v.a + j], -1, lab);
+        bad = vb && !ok;
+      } else if (v.kind == KSS_VOL_ZONE) {
+        if (vz && zoned)
+          for (int j = 0; j < v.b && !bad; j++) bad = !req_match_t(c, job.P.ints, job.P.reqs[v.a + j], -1, lab);
+      } else if (v.kind == KSS_VOL_ZONE_ERROR) {
+        bad = vz && zoned;
+      }
+    }
+    if (bad) st_ag(wp, (w & (SW_AFF_OK | SW_TAINT_OK)) | SW_VOLUME_STATIC);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // as k_static: agent-scope stores, ordered by the kernel boundary
+}
+
+static void launch_static_vol(hipStream_t st, const DevJob* jobs, const kss_profile& pr, int k0, int k1, int n_lo, int n_hi,
+                              const SVolLaunch* vl) {
+  const dim3 grid((unsigned)(std::max(n_hi - n_lo, 1) + 255) / 256, (unsigned)((k1 - k0 + STATIC_PODS - 1) / STATIC_PODS));
+  hipLaunchKernelGGL(k_static_vol, grid, dim3(256), 0, st, jobs, pr, k0, k1, n_lo, n_hi, vl);
+}
+
+// The node-state columns of the form, packed from vol_count / vol_attached / vol_limit before a
+// batch's first launch (one lane per node): the rows with a pod on the node, the attached counts and
+// the limits as 16-bit fields (a limit below 0, "not limited", as SV_UNCHECKED).  chk: per key the
+// largest attached count [0 .. SV_KEYS) and limit [SV_KEYS .. 2 SV_KEYS) met, for the host's overflow
+// check (vol_fields_fit) -- a value that does not fit is clamped here and refused there.
+__global__ __launch_bounds__(256) void k_vol_pack(DevCluster c, uint64_t* used, uint64_t* att, uint64_t* lim, int32_t* chk) {
+  const int n = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (n >= c.N) return;
+  const size_t N = (size_t)c.N;
+  uint64_t u = 0, a[2] = {0, 0}, l[2] = {0, 0};
+  for (int r = 0; r < c.n_vol_rows && r < SV_ROWS; r++) u |= c.vol_count[(size_t)r * N + n] > 0 ? 1ull << r : 0ull;
+  for (int k = 0; k < c.n_vol_keys && k < SV_KEYS; k++) {
+    const int32_t av = c.vol_attached[(size_t)k * N + n], lv = c.vol_limit[(size_t)k * N + n];
+    atomicMax(&chk[k], av);
+    atomicMax(&chk[SV_KEYS + k], lv);
+    const uint64_t af = (uint64_t)min(max(av, 0), (int32_t)SV_FIELD_MAX);
+    const uint64_t lf = lv < 0 ? (uint64_t)SV_UNCHECKED : (uint64_t)min(lv, (int32_t)SV_FIELD_MAX);
+    a[k >> 2] |= af << (16 * (k & 3));
+    l[k >> 2] |= lf << (16 * (k & 3));
+  }
+  used[n] = u;
+  att[n] = a[0];
+  att[N + n] = a[1];
+  lim[n] = l[0];
+  lim[N + n] = l[1];
+}
+
+// After the batch's last launch: vol_attached back from the packed fields (one lane per node) ...
+__global__ __launch_bounds__(256) void k_vol_unpack(const DevJob* __restrict__ jobs, const uint64_t* att) {
+  const DevCluster& c = jobs[0].c;
+  const int n = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (n >= c.N) return;
+  const size_t N = (size_t)c.N;
+  const uint64_t a[2] = {ld_ag(&att[n]), ld_ag(&att[N + n])};
+  for (int k = 0; k < c.n_vol_keys && k < SV_KEYS; k++)
+    c.vol_attached[(size_t)k * N + n] = (int32_t)((a[k >> 2] >> (16 * (k & 3))) & 0xFFFFu);
+}
+
+// ... and vol_count[row][chosen] += 1 for every KSS_VOL_OWN entry of every scheduled pod (one lane
+// per pod, beside k_counts; several pods choose one node: atomic adds).  The loop reads no count
+// (its used-rows word has the bit), so like the class / term counts they wait for the last chunk.
+__global__ __launch_bounds__(256) void k_vol_counts(const DevJob* __restrict__ jobs, int n_pods) {
+  const DevJob& job = jobs[0];
+  const int k = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (k >= min(n_pods, job.n_pods)) return;
+  const int x = job.chosen[k] - job.c.node_base;
+  if (x < 0 || x >= job.c.N) return;
+  const kss_pod& p = job.P.pods[k];
+  for (int e = 0; e < p.vol_len; e++) {
+    const kss_vol& v = job.P.vols[p.vol_off + e];
+    if (v.kind == KSS_VOL_OWN) atomicAdd(&job.c.vol_count[(size_t)v.row * (size_t)job.c.N + x], 1);
+  }
+}
+
+static void launch_vol_writeback(hipStream_t st, const DevJob* jobs, int n_nodes, int n_pods, const SVolLaunch* vl) {
+  // (the block's layout: vol_pack_state)
+  const VolStateLayout L((size_t)std::max(n_nodes, 1));
+  const uint64_t* att = (const uint64_t*)((const char*)vl + L.o_att);
+  hipLaunchKernelGGL(k_vol_unpack, dim3((unsigned)(std::max(n_nodes, 1) + 255) / 256), dim3(256), 0, st, jobs, att);
+  hipLaunchKernelGGL(k_vol_counts, dim3((unsigned)(std::max(n_pods, 1) + 255) / 256), dim3(256), 0, st, jobs, n_pods);
 }

@@ -251,6 +251,42 @@ struct alignas(16) SPort {
 };
 static_assert(sizeof(SPort) == 16, "SPort is copied as uint4");
 
+// The volumes form (VOL: k_static_vol, k_simple_vol; option simple_volumes), a variant of the PI
+// form.  In a batch that only commits the volume filters never read a count: VolumeRestrictions
+// reads vol_count[row][n] > 0, the limit plugins vol_count[row][n] == 0, vol_attached[key][n] and
+// vol_limit[key][n], and AssumePod only ever turns a row's bit on.  So a node's volume state is one
+// word of used rows (<= SV_ROWS rows) and one SV_FIELD-bit counter and limit per limit key (<=
+// SV_KEYS keys, four per 64-bit word; the host checks that no field can overflow), and a pod's
+// volume program is masks over the rows and counts per key: a parallel array beside SPod, like
+// SPort, with a ring of its own in LDS.
+constexpr int SV_KEYS = 8, SV_ROWS = 64;
+constexpr uint32_t SV_UNCHECKED = 0xFFFFu;  // a limit field of vol_limit < 0 (the node does not limit the key)
+constexpr uint32_t SV_FIELD_MAX = 0xFFFEu;  // the largest counter / limit a field holds
+constexpr uint32_t SV_STATIC = 1u << 8;     // SVol::keys: the pod has VolumeBinding / VolumeZone entries (k_static_vol)
+struct alignas(16) SVol {
+  uint64_t conflict;  // rows of its KSS_VOL_CONFLICT entries
+  uint64_t shared;    // rows of its KSS_VOL_LIMIT entries with row >= 0
+  uint64_t own;       // rows of its KSS_VOL_OWN entries
+  uint32_t keys;      // bits 0-7: keys with a KSS_VOL_LIMIT entry (checked only then); SV_STATIC; bits 16-23:
+                      // keys its commit can add to (an own row of the key, or a KSS_VOL_OWN_PRIVATE count)
+  uint32_t pad;
+  uint16_t pnew[SV_KEYS];  // per key, the sum of `count` of its KSS_VOL_LIMIT entries with row < 0
+  uint16_t padd[SV_KEYS];  // per key, its KSS_VOL_OWN_PRIVATE count
+};
+static_assert(sizeof(SVol) == 64, "SVol is copied as four uint4");
+// One launch's constants and node-state columns of the form (a kernel argument by value).
+struct SVolLaunch {
+  uint64_t keyrows[SV_KEYS];  // per key, the rows counted under it (vol_row_key)
+  uint32_t key_on;            // keys whose plugin the profile enables
+  uint32_t key_csi;           // keys of NodeVolumeLimits (CSI: a key without a new volume is not checked)
+  uint32_t vr_on;             // VolumeRestrictions enabled
+  uint32_t pad;
+  uint64_t* used;             // [N] rows with vol_count > 0
+  uint64_t* att;              // [2][N] packed vol_attached, key k in word k / 4 at bit 16 * (k % 4)
+  uint64_t* lim;              // [2][N] packed vol_limit (SV_UNCHECKED: < 0)
+  const SVol* svols;          // [n_pods]
+};
+
 // lab(key): the node's interned label value (label_of by default; k_static reads an LDS copy)
 template <class Lab>
 __device__ __forceinline__ uint32_t static_word_l(const DevCluster& c, const DevPods& P, const kss_pod& p,
@@ -946,6 +982,12 @@ __host__ __device__ inline size_t simple_lds_bytes_pi(int cap, int nsc) {
   return (simple_lds_bytes(cap, nsc) + 15) / 16 * 16 + RING * sizeof(SPort) + 8 * (size_t)cap;
 }
 
+// The volumes form's LDS behind the PI form's: the used-rows column, the packed attached / limit
+// columns (two words each), the keys' row masks, and the ring of the pods' SVol records.
+__host__ __device__ inline size_t simple_lds_bytes_vol(int cap, int nsc) {
+  return (simple_lds_bytes_pi(cap, nsc) + 15) / 16 * 16 + 40 * (size_t)cap + 8 * SV_KEYS + RING * sizeof(SVol);
+}
+
 struct ShapeTab {
   uint64_t* shp;   // [SSHAPE_WORDS][n_shapes]: the shapes' SShape records, staged once per launch, word by word
                    // (lane = shape reads consecutive words: no bank conflict)
@@ -1102,16 +1144,89 @@ __device__ __forceinline__ void pi_fix(const kss_profile& prof, SVal& e, uint64_
   e.fit |= il << 8;
 }
 
+// The volumes form's LDS (simple_lds_bytes_vol) and launch constants as pass A and the commit see them.
+struct VolView {
+  uint64_t* used;         // [cap]
+  uint64_t* att;          // [2][cap]
+  uint64_t* lim;          // [2][cap]
+  const uint64_t* keyrows;  // [SV_KEYS]
+  SVol* ring;             // [RING]
+  uint32_t key_on, key_csi, vr_on;
+  int cap;
+};
+__device__ __forceinline__ VolView vol_view(uint8_t* smem0, int cap, int nsc, const SVolLaunch& K) {
+  uint8_t* b = smem0 + (simple_lds_bytes_pi(cap, nsc) + 15) / 16 * 16;
+  VolView V;
+  V.cap = cap;
+  V.used = reinterpret_cast<uint64_t*>(b);
+  V.att = V.used + cap;
+  V.lim = V.att + 2 * (size_t)cap;
+  uint64_t* kr = V.lim + 2 * (size_t)cap;
+  V.keyrows = kr;
+  V.ring = reinterpret_cast<SVol*>(kr + SV_KEYS);
+  V.key_on = K.key_on;
+  V.key_csi = K.key_csi;
+  V.vr_on = K.vr_on;
+  return V;
+}
+
+// AssumePod of pod p's volumes on a node's state in registers (vol_commit_row over its KSS_VOL_OWN
+// rows, then its KSS_VOL_OWN_PRIVATE counts): a row not yet used adds one to its key's counter,
+// then the row is used.  The key mask is wave-uniform: a scalar loop over its set bits.
+__device__ __forceinline__ void vol_assume(const VolView& V, const SVol& p, uint64_t& used, uint64_t& a0, uint64_t& a1) {
+  const uint64_t own = p.own;
+  for (uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)((p.keys >> 16) & 0xFFu)); m; m &= m - 1) {
+    const int k = __builtin_ctz(m), sh = (k & 3) * 16;
+    const uint64_t d = (uint64_t)(__builtin_popcountll(own & ~used & V.keyrows[k]) + (int)p.padd[k]) << sh;
+    if (k < 4) a0 += d;
+    else a1 += d;
+  }
+  used |= own;
+}
+
+// The dynamic volume filters of pod q (ring slot vq) on slot ns: VolumeRestrictions (a row of its
+// conflict mask is used) and the attach-limit plugins, limit_exceeded (kss_eval.cuh) restated on the
+// packed fields for every key of the pod's key mask.  extra: the H1 evaluation, on the state after
+// pod p's (ring slot vp) AssumePod.
+__device__ __forceinline__ bool vol_infeasible(const VolView& V, int ns, bool extra, int vq, int vp) {
+  const SVol& q = V.ring[vq];
+  uint64_t used = V.used[ns], a0 = V.att[ns], a1 = V.att[V.cap + ns];
+  const uint64_t l0 = V.lim[ns], l1 = V.lim[V.cap + ns];
+  if (extra) vol_assume(V, V.ring[vp], used, a0, a1);
+  bool bad = V.vr_on && (used & q.conflict) != 0;
+  const uint64_t fresh = q.shared & ~used;
+  for (uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)(q.keys & 0xFFu & V.key_on)); m; m &= m - 1) {
+    const int k = __builtin_ctz(m), sh = (k & 3) * 16;
+    const uint32_t a = (uint32_t)((k < 4 ? a0 : a1) >> sh) & 0xFFFFu, l = (uint32_t)((k < 4 ? l0 : l1) >> sh) & 0xFFFFu;
+    const uint32_t nw = (uint32_t)__builtin_popcountll(fresh & V.keyrows[k]) + q.pnew[k];
+    const bool csi = (V.key_csi >> k) & 1u;
+    bad |= l != SV_UNCHECKED && !(csi && nw == 0) && a + nw > l;
+  }
+  return bad;
+}
+
+// ... and pod p's AssumePod on slot s of the columns (simple_commit_lanes, one lane)
+__device__ __forceinline__ void vol_commit(const VolView& V, int s, int vp) {
+  uint64_t used = V.used[s], a0 = V.att[s], a1 = V.att[V.cap + s];
+  vol_assume(V, V.ring[vp], used, a0, a1);
+  V.used[s] = used;
+  V.att[s] = a0;
+  V.att[V.cap + s] = a1;
+}
+
 // Pass A for pod q (static words in ring slot `sl`) over the shard's `own` nodes on the
 // current state (H0), plus the candidate slot `cand_s` (-1 none) re-evaluated with the
 // previous pod `q0` committed on it (H1), by the first slot without a node (slot `own`,
 // which is slot `cap` of lane 0 when the shard is full).  st = {nf0, tt0, na0, nf1, tt1, na1}.
 // Both records are copied to registers before the node loop (its LDS stores would otherwise
 // make the compiler re-read every record field inside the loop, one LDS round trip each).
-template <bool DEF, bool PI = false>
+// VOL (all four pass-A functions): the volumes form; a node that passed so far fails on pod q's
+// dynamic volume filters (vol_infeasible; V: the columns, vq / vp: the ring slots of q's and q0's SVol).
+template <bool DEF, bool PI = false, bool VOL = false>
 __device__ __forceinline__ void simple_pass_a(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                               const SimpleShard& L, int sl, int own, int cand_s, long long (&st)[6],
-                                              const uint64_t* pused = nullptr, SPort qp = SPort{}, uint64_t q0add = 0) {
+                                              const uint64_t* pused = nullptr, SPort qp = SPort{}, uint64_t q0add = 0,
+                                              const VolView* V = nullptr, int vq = 0, int vp = 0) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1132,6 +1247,7 @@ __device__ __forceinline__ void simple_pass_a(const kss_profile& prof, const SPo
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
     if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
+    if constexpr (VOL) e.f = (e.f == 0 && vol_infeasible(*V, ns, extra, vq, vp)) ? KSS_F_VOLUME_RESTRICTIONS : e.f;
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap : s, e);
     // H0 counts the shard's own slots, H1 every slot but the candidate's (whose H1 value is
@@ -1158,11 +1274,11 @@ __device__ __forceinline__ void simple_pass_a(const kss_profile& prof, const SPo
 // reduces its best key by itself: the waves' bests ride with the statistics, one workgroup
 // reduction per pod instead of two (simple_sync_pw).  u = the wave lane's {nf0, tt0, na0, nf1,
 // tt1, na1} (H1: the wave's slots but its candidate, plus the candidate re-evaluated).
-template <bool DEF, bool PI = false>
+template <bool DEF, bool PI = false, bool VOL = false>
 __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                                  const SimpleShard& L, int sl, int own, int pwv, int cand_w,
                                                  uint32_t (&u)[6], const uint64_t* pused = nullptr, SPort qp = SPort{},
-                                                 uint64_t q0add = 0) {
+                                                 uint64_t q0add = 0, const VolView* V = nullptr, int vq = 0, int vp = 0) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1185,6 +1301,7 @@ __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const 
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
     if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
+    if constexpr (VOL) e.f = (e.f == 0 && vol_infeasible(*V, ns, extra, vq, vp)) ? KSS_F_VOLUME_RESTRICTIONS : e.f;
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap + wv : s, e);
     const bool c0 = e.f == 0 && !extra, c1 = e.f == 0 && (extra || s != cand_w);
@@ -1204,12 +1321,16 @@ __device__ __forceinline__ void simple_pass_a_pw(const kss_profile& prof, const 
 // following each other on one lane (r7c A/B against one lane adding every row: C2 284.7k ->
 // 290.7k pods/s, C4 unchanged; the one-lane form is retired, DESIGN.md "Retired A/B switches").
 static_assert(offsetof(SPod, cnz) == offsetof(SPod, creq) + 3 * sizeof(double), "creq, cnz adjacent");
-template <bool PI = false>
+template <bool PI = false, bool VOL = false>
 __device__ __forceinline__ void simple_commit_lanes(const SimpleShard& L, const SPod& pk, int s, int lane,
-                                                    uint64_t* pused = nullptr, uint64_t padd = 0) {
+                                                    uint64_t* pused = nullptr, uint64_t padd = 0,
+                                                    const VolView* V = nullptr, int vp = 0) {
   const int cap = L.cap;
   if constexpr (PI) {  // NodeInfo.UsedPorts: the pod's host ports
     if (lane == 6) pused[s] |= padd;
+  }
+  if constexpr (VOL) {  // the pod's volumes, on the free lane next to it
+    if (lane == 7) vol_commit(*V, s, vp);
   }
   if (lane < 5) L.r64[(3 + lane) * cap + s] += (&pk.creq[0])[lane];
   if (lane == 5) L.r32[s] += 1;
@@ -1227,13 +1348,13 @@ __device__ __forceinline__ void simple_commit_lanes(const SimpleShard& L, const 
 // wave polling for itself, with no closing barrier, lost (r8t A/B: C2 261k against 304k pods/s):
 // the prefetch waves' polls queue behind their own HBM prefetch loads (vmcnt is in order), so
 // the pod waits for them.  (Retired: DESIGN.md "Retired A/B switches".)
-template <bool PI = false, typename Idle>
+template <bool PI = false, bool VOL = false, typename Idle>
 __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long long wbest, uint32_t (&u)[6], int W,
                                                int w, unsigned epoch, unsigned long long* gran, const XPeers& X,
                                                int* err, int per, int node_base, int lo, int own, const SPod& pk,
                                                bool commit, const SimpleShard& L, int kb, long long (&R)[4],
                                                KSS_GLOBAL unsigned long long* sp, Idle&& idle,
-                                               uint64_t* pused = nullptr, uint64_t padd = 0) {
+                                               uint64_t* pused = nullptr, uint64_t padd = 0, const VolView* V = nullptr, int vp = 0) {
   wave_red_stats_pw(u);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   if (sp && threadIdx.x == 0) sp[7] = wall_clock64();
@@ -1283,13 +1404,13 @@ __device__ __forceinline__ bool simple_sync_pw(SimpleHdr& H, int& parity, long l
         H.res[2] = h1 ? t[4] : t[1];
         H.res[3] = h1 ? t[5] : t[2];
       }
-      if (commit && h1) simple_commit_lanes<PI>(L, pk, slot, lane, pused, padd);
+      if (commit && h1) simple_commit_lanes<PI, VOL>(L, pk, slot, lane, pused, padd, V, vp);
     } else {
       const long long v[7] = {best, t[0], t[1], t[2], t[3], t[4], t[5]};
       if (simple_exchange(H, gran, X, W, w, epoch, err, v, per, node_base, kb) && commit) {
         const long long K = H.res[0];  // (written by lane 0 of this wave: in order)
         const int x = key_node(K, node_base, lo);
-        if (x >= 0 && x < own) simple_commit_lanes<PI>(L, pk, x, lane, pused, padd);
+        if (x >= 0 && x < own) simple_commit_lanes<PI, VOL>(L, pk, x, lane, pused, padd, V, vp);
       }
     }
   }
@@ -1341,11 +1462,11 @@ __device__ __forceinline__ void win_acc(uint32_t (&u)[12], bool c0, bool c1, int
 }
 
 // simple_pass_a with the window's split: part a / b of each slot by its node against `start`
-template <bool DEF, bool PI = false>
+template <bool DEF, bool PI = false, bool VOL = false>
 __device__ __forceinline__ void simple_pass_a_win(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                                   const SimpleShard& L, int sl, int own, int cand_s, int lo, int start,
                                                   uint32_t (&u)[12], const uint64_t* pused = nullptr, SPort qp = SPort{},
-                                                  uint64_t q0add = 0) {
+                                                  uint64_t q0add = 0, const VolView* V = nullptr, int vq = 0, int vp = 0) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1366,6 +1487,7 @@ __device__ __forceinline__ void simple_pass_a_win(const kss_profile& prof, const
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
     if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
+    if constexpr (VOL) e.f = (e.f == 0 && vol_infeasible(*V, ns, extra, vq, vp)) ? KSS_F_VOLUME_RESTRICTIONS : e.f;
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap : s, e);
     win_acc(u, e.f == 0 && !extra, e.f == 0 && s != cand_s, lo + ns >= start ? 0 : 1, e);
@@ -1373,11 +1495,12 @@ __device__ __forceinline__ void simple_pass_a_win(const kss_profile& prof, const
 }
 
 // simple_pass_a_pw with the window's split
-template <bool DEF, bool PI = false>
+template <bool DEF, bool PI = false, bool VOL = false>
 __device__ __forceinline__ void simple_pass_a_pw_win(const kss_profile& prof, const SPod& q_lds, const SPod& q0_lds,
                                                      const SimpleShard& L, int sl, int own, int pwv, int cand_w, int lo,
                                                      int start, uint32_t (&u)[12], const uint64_t* pused = nullptr,
-                                                     SPort qp = SPort{}, uint64_t q0add = 0) {
+                                                     SPort qp = SPort{}, uint64_t q0add = 0, const VolView* V = nullptr,
+                                                     int vq = 0, int vp = 0) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t* sw = L.st + (size_t)sl * L.cap;
   const SPod q = q_lds;
@@ -1399,6 +1522,7 @@ __device__ __forceinline__ void simple_pass_a_pw_win(const kss_profile& prof, co
     if (extra) add_commit(r, q0);
     SVal e = DEF ? dyn_eval_def(q, wd, r) : dyn_eval(prof, q, wd, r);
     if constexpr (PI) pi_fix<DEF>(prof, e, pused[ns] | (extra ? q0add : 0ull), qp.conflict);
+    if constexpr (VOL) e.f = (e.f == 0 && vol_infeasible(*V, ns, extra, vq, vp)) ? KSS_F_VOLUME_RESTRICTIONS : e.f;
     if (scal && e.f == 0 && scalar_short(L.sc, L.nsc, L.cap, ns, q_lds, extra, q0_lds)) e.f = KSS_F_NODE_RESOURCES_FIT;
     cv_put(L, extra ? L.cap + wv : s, e);
     win_acc(u, e.f == 0 && !extra, e.f == 0 && (extra || s != cand_w), lo + ns >= start ? 0 : 1, e);
@@ -1520,14 +1644,14 @@ __device__ __forceinline__ void win_cut_scan(SimpleHdr& H, const SimpleShard& L,
 // k+1's cut segment (part * W + shard, -1: no cut), d_out = its dropped node (on the cut shard;
 // -1 elsewhere).  start: this shard's split of pod k+1's node list (win_start).  False if the
 // launch aborted.
-template <bool PW, bool PI = false, typename Idle>
+template <bool PW, bool PI = false, bool VOL = false, typename Idle>
 __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long long wkey, uint32_t (&u)[12], int W,
                                                 int w, unsigned epoch, unsigned long long* gran, const XPeers& X,
                                                 int* err, int per, int node_base, int lo, int own, const SPod& pk,
                                                 bool commit, const SimpleShard& L, int kb, int k_find, int start,
                                                 int pwv, long long (&R)[4], int& d_out, int& cs_out,
                                                 KSS_GLOBAL unsigned long long* sp, Idle&& idle,
-                                                uint64_t* pused = nullptr, uint64_t padd = 0) {
+                                                uint64_t* pused = nullptr, uint64_t padd = 0, const VolView* V = nullptr, int vp = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   if (PW) {
     // one node (or the H1 re-evaluation) per lane: the four counts are ballot popcounts, the four
@@ -1778,7 +1902,7 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
       // reads that row without a barrier of its own)
       if (commit && gbest != 0) {
         const int x = gl - lo;
-        if (x >= 0 && x < own) simple_commit_lanes<PI>(L, pk, x, lane, pused, padd);
+        if (x >= 0 && x < own) simple_commit_lanes<PI, VOL>(L, pk, x, lane, pused, padd, V, vp);
       }
       if (lane == 0) {
         H.res[0] = gbest;
@@ -1874,14 +1998,26 @@ __device__ __forceinline__ bool simple_sync_win(SimpleHdr& H, int& parity, long 
 // the same hand-off), committed with the row (simple_commit_lanes: same wave, same place relative
 // to the barriers), read by pass A next to the row -- H1 with pod k's port_add ORed in, as H1 adds
 // pod k's requests to the row.  The masks' ring is stored where the record ring is.
-template <bool DEF, bool PW, bool WIN, bool PI = false>
+// VOL (with PI): the volumes form (k_simple_vol).  The static words are k_static_pi's with
+// k_static_vol's VolumeBinding / VolumeZone verdicts; vl holds the pods' SVol records, the launch's
+// constants and the node-state columns in HBM (packed before the batch's first launch, unpacked
+// after its last: a chunked batch carries them from launch to launch as it carries UsedPorts).
+// The used-rows / attached / limit columns are node state exactly like `pused`: loaded where it is
+// loaded, written back where it is written back, committed by the lane next to its lane in
+// simple_commit_lanes (same wave, same place relative to the barriers) and read by pass A where it
+// is read -- H1 on the state after pod k's AssumePod, applied in registers (vol_assume).  The SVol
+// ring is stored and read behind the same barriers as the SPort ring.  So what holds for `pused`
+// above holds for them: no barrier of their own.
+template <bool DEF, bool PW, bool WIN, bool PI = false, bool VOL = false>
 __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __restrict__ spods,
                                                 const uint32_t* __restrict__ stat, const int32_t* __restrict__ ints,
                                                 int k0, int k1, int32_t* chosen, PodMeta* meta, const kss_profile& prof,
                                                 int W, int w, int cap, unsigned long long* gran, const XPeers& X,
                                                 unsigned epoch0, int* err, unsigned long long* stamps, long long* smem,
                                                 int k_find = 0, int32_t* cursor = nullptr,
-                                                const SPort* __restrict__ sports = nullptr) {
+                                                const SPort* __restrict__ sports = nullptr,
+                                                const SVolLaunch* vl = nullptr) {
+  static_assert(!VOL || PI, "the volumes form is a variant of the ports-and-images form");
   const int tid = threadIdx.x, nt = blockDim.x;
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
   const SimpleShard L = shard_view(reinterpret_cast<uint8_t*>(smem) + sizeof(SimpleHdr), cap, c.n_scalar);
@@ -1889,6 +2025,10 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       PI ? reinterpret_cast<SPort*>(reinterpret_cast<uint8_t*>(smem) + (simple_lds_bytes(cap, c.n_scalar) + 15) / 16 * 16)
          : nullptr;
   uint64_t* const pused = PI ? reinterpret_cast<uint64_t*>(pring + RING) : nullptr;
+  VolView VV{};
+  if constexpr (VOL) VV = vol_view(reinterpret_cast<uint8_t*>(smem), cap, c.n_scalar, *vl);
+  const VolView* const V = VOL ? &VV : nullptr;
+  constexpr int NV = (int)(sizeof(SVol) / 16);
   const size_t N = (size_t)c.N;
   const int per = (c.N + W - 1) / W;
   const int lo = min(c.N, w * per), hi = min(c.N, lo + per), own = hi - lo;
@@ -1919,6 +2059,14 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     }
     for (int d = 0; d < PD && k0 + d < k1; d++) L.st[((k0 + d) % RING) * cap + s] = ld_ag(&stat[(size_t)d * N + lo + s]);
     if constexpr (PI) pused[s] = ld_ag(&c.port_used[n]);
+    if constexpr (VOL) {
+      VV.used[s] = ld_ag(&vl->used[n]);
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        VV.att[h * cap + s] = ld_ag(&vl->att[h * N + n]);
+        VV.lim[h * cap + s] = vl->lim[h * N + n];
+      }
+    }
   }
   for (int i = tid; i < min(k1 - k0, PD) * NQ; i += nt) {
     const int j = k0 + i / NQ;
@@ -1926,8 +2074,17 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
   }
   if constexpr (PI) {
     for (int i = tid; i < RING; i += nt) pring[i] = SPort{};  // (the prologue iteration reads the slot of pod k0 - 1)
+    if constexpr (VOL) {
+      for (int i = tid; i < RING * NV; i += nt) reinterpret_cast<uint4*>(VV.ring)[i] = make_uint4(0, 0, 0, 0);
+      if (tid < SV_KEYS) const_cast<uint64_t*>(VV.keyrows)[tid] = vl->keyrows[tid];
+    }
     __syncthreads();
     for (int i = tid; i < min(k1 - k0, PD); i += nt) pring[(k0 + i) % RING] = sports[k0 + i];
+    if constexpr (VOL) {
+      for (int i = tid; i < min(k1 - k0, PD) * NV; i += nt)
+        reinterpret_cast<uint4*>(VV.ring + (k0 + i / NV) % RING)[i % NV] =
+            reinterpret_cast<const uint4*>(vl->svols + k0 + i / NV)[i % NV];
+    }
   }
   if (tid == 0) H.abort = 0;
   __syncthreads();
@@ -1946,6 +2103,8 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
   KSS_GLOBAL unsigned long long* gstamps = gp(stamps);
   KSS_GLOBAL const uint4* gsport = gp(reinterpret_cast<const uint4*>(sports));
   uint4 pfp = make_uint4(0, 0, 0, 0);  // PI: the prefetched port masks of pod k+PD
+  KSS_GLOBAL const uint4* gsvol = gp(reinterpret_cast<const uint4*>(VOL ? vl->svols : nullptr));
+  uint4 pfv = make_uint4(0, 0, 0, 0);  // VOL: a quarter of its SVol (prefetch lanes 0 .. NV - 1)
   long long st[6], R[4] = {0, 0, 0, 0};
   // the outcome of pod pend_k, not yet stored (thread out_tid of shard w_off)
   const int out_tid = (nt >> 6) > 1 ? 64 : 0;
@@ -2009,6 +2168,10 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
           KSS_GLOBAL const uint4& ps = gsport[(size_t)(k + PD)];
           pfp = make_uint4(ps.x, ps.y, ps.z, ps.w);
         }
+        if constexpr (VOL) {
+          KSS_GLOBAL const uint4& vs = gsvol[(size_t)(k + PD) * NV + min(pf_lane, NV - 1)];
+          pfv = make_uint4(vs.x, vs.y, vs.z, vs.w);
+        }
 #pragma unroll
         for (int j = 0; j < PF_MAX; j++)
           if (j < pf_per) pfw[j] = ld_ag(&gstat[(size_t)(k + PD - k0) * N + lo + min(j * pf_n + pf_lane, own - 1)]);
@@ -2019,6 +2182,9 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
         reinterpret_cast<uint4*>(L.ring + (k + PD) % RING)[min(pf_lane, NQ - 1)] = pfq;
         if constexpr (PI) {
           if (pf_lane == 0) *reinterpret_cast<uint4*>(pring + (k + PD) % RING) = pfp;
+        }
+        if constexpr (VOL) {
+          if (pf_lane < NV) reinterpret_cast<uint4*>(VV.ring + (k + PD) % RING)[pf_lane] = pfv;
         }
 #pragma unroll
         for (int j = 0; j < PF_MAX; j++)
@@ -2096,6 +2262,7 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     // reads, here and not at the top: like qn, pod k+1's slot is behind pass B's barrier (not PW)
     const uint64_t pk_add = PI ? pring[(k + RING) % RING].add : 0ull;
     const SPort qnp = PI ? pring[(k + 1) % RING] : SPort{};
+    const int vqn = (k + 1) % RING, vpk = (k + RING) % RING;  // VOL: the SVol ring slots of pod k+1 and pod k
     if constexpr (WIN) {
       // pod k+1 starts where pod k's window stopped (its dropped node, on the cut shard), else
       // where pod k started
@@ -2106,31 +2273,31 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       }
       uint32_t u[12];
       if (k + 1 < k1) {
-        if constexpr (PW) simple_pass_a_pw_win<DEF, PI>(prof, qn, pk, L, sln, own, pwv, cand, lo, wsl, u, pused, qnp, pk_add);
-        else simple_pass_a_win<DEF, PI>(prof, qn, pk, L, sln, own, cand, lo, wsl, u, pused, qnp, pk_add);
+        if constexpr (PW) simple_pass_a_pw_win<DEF, PI, VOL>(prof, qn, pk, L, sln, own, pwv, cand, lo, wsl, u, pused, qnp, pk_add, V, vqn, vpk);
+        else simple_pass_a_win<DEF, PI, VOL>(prof, qn, pk, L, sln, own, cand, lo, wsl, u, pused, qnp, pk_add, V, vqn, vpk);
       } else {
 #pragma unroll
         for (int i = 0; i < 12; i++) u[i] = 0;
       }
       if (sp && tid == 0) sp[3] = wall_clock64();
-      if (!simple_sync_win<PW, PI>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0,
-                                   L, kb, k_find, wsl, pwv, R, wd, wcs, sp, prefetch_idle, pused, pk_add))
+      if (!simple_sync_win<PW, PI, VOL>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0,
+                                   L, kb, k_find, wsl, pwv, R, wd, wcs, sp, prefetch_idle, pused, pk_add, V, vpk))
         return;
     } else if constexpr (PW) {
       uint32_t u[6];
       if (k + 1 < k1) {
-        simple_pass_a_pw<DEF, PI>(prof, qn, pk, L, sln, own, pwv, cand, u, pused, qnp, pk_add);
+        simple_pass_a_pw<DEF, PI, VOL>(prof, qn, pk, L, sln, own, pwv, cand, u, pused, qnp, pk_add, V, vqn, vpk);
       } else {
 #pragma unroll
         for (int i = 0; i < 6; i++) u[i] = 0;
       }
       if (sp && tid == 0) sp[3] = wall_clock64();
-      if (!simple_sync_pw<PI>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0, L, kb,
-                              R, sp, prefetch_idle, pused, pk_add))
+      if (!simple_sync_pw<PI, VOL>(H, parity, best, u, W, w, ++epoch, gran, X, err, per, c.node_base, lo, own, pk, k >= k0, L, kb,
+                              R, sp, prefetch_idle, pused, pk_add, V, vpk))
         return;
     } else {
       if (k + 1 < k1) {
-        simple_pass_a<DEF, PI>(prof, qn, pk, L, sln, own, cand, st, pused, qnp, pk_add);
+        simple_pass_a<DEF, PI, VOL>(prof, qn, pk, L, sln, own, cand, st, pused, qnp, pk_add, V, vqn, vpk);
       } else {
 #pragma unroll
         for (int i = 0; i < 6; i++) st[i] = 0;
@@ -2147,7 +2314,7 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       const bool won = x >= lo && x < hi;
       sub_s = won ? x - lo : -1;
       sub_h = PW ? cap + (won ? (x - lo) / max(pwv, 1) : 0) : cap;
-      if (!PW && !WIN && won && tid < 64) simple_commit_lanes<PI>(L, pk, x - lo, tid, pused, pk_add);
+      if (!PW && !WIN && won && tid < 64) simple_commit_lanes<PI, VOL>(L, pk, x - lo, tid, pused, pk_add, V, vpk);
       // the HBM-only class / term counts are applied after the launch (k_counts): nothing in
       // this loop reads them
     }
@@ -2217,6 +2384,11 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
     st_ag(&c.pod_count[n], L.r32[s]);
     for (int i = 0; i < L.nsc; i++) st_ag(&c.requested[(size_t)(3 + i) * N + n], L.sc[(size_t)(L.nsc + i) * cap + s]);
     if constexpr (PI) st_ag(&c.port_used[n], pused[s]);
+    if constexpr (VOL) {
+      st_ag(&vl->used[n], VV.used[s]);
+      st_ag(&vl->att[n], VV.att[s]);
+      st_ag(&vl->att[N + n], VV.att[cap + s]);
+    }
   }
   handoff_release();
 }

@@ -86,6 +86,7 @@ SIGNATURES = [
     ("kss_last_xcd_local", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_shape_table", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_simple_exchange", C.c_int, [C.c_void_p, P(C.c_int32)]),
+    ("kss_last_simple_form", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_plan_shapes", C.c_int, [C.POINTER(abi.PodSet), C.c_int32, P(C.c_int32), P(C.c_int32)]),
     ("kss_device_go_log", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     ("kss_plan_podset", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.c_void_p]),
@@ -708,6 +709,13 @@ class Context:
         out = (C.c_int32 * 2)()
         check(lib().kss_last_simple_exchange(self.h, out))
         return {"flat": out[0], "entries": out[1]}
+
+    def last_simple_form(self) -> Dict[str, int]:
+        """{volumes, lds_bytes} of the last run (kss_last_simple_form): volumes 1 when k_simple ran its
+        volumes form (option simple_volumes), lds_bytes the loop kernel's dynamic LDS per workgroup."""
+        out = (C.c_int32 * 2)()
+        check(lib().kss_last_simple_form(self.h, out))
+        return {"volumes": out[0], "lds_bytes": out[1]}
 
     def last_kernel(self) -> str:
         k = lib().kss_last_kernel(self.h)
