@@ -1043,6 +1043,32 @@ const char* kss_plan_reason(int32_t code);
  * PodTopologySpread's topologyNormalizingWeight in k_spread) at x[i], i < n, evaluated on
  * `device`; host arrays.  Compared bitwise with the host port (kss_go_log_c) by the tests. */
 int kss_device_go_log(int32_t device, const double* x, double* y, int32_t n);
+/* Test support: out[i] = one primitive of the exact-division set (kss_fastmath.cuh, least_bf of
+ * kss_simple.cuh, div_i64 / div_f53 of kss_eval.cuh) at (a[i], b[i]), i < n, evaluated on `device` by
+ * the functions the scheduling kernels call, with the reciprocal formed as those kernels form it:
+ * v_rcp_f32 of (float)b for small_div, the device's f64 division 1.0 / (double)b for the others.
+ * Operands are int64 (converted to double where the primitive takes doubles); 0 <= a, 0 < b, and
+ * both below 2^31 for KSS_FM_SMALL_DIV / KSS_FM_RCP_F32, else KSS_E_INVAL.  a is the dividend (the
+ * quotient ops), or the requested amount with b the capacity (least_bf and the alloc_score ops).
+ * The double results (DIV_RN_D, DIV_RN, RCP_F64) and RCP_F32 come back as their bit patterns. */
+enum {
+  KSS_FM_SMALL_DIV = 0,      /* small_div(a, b, rcp) */
+  KSS_FM_QUOT_SMALL_D,       /* quot_small_d */
+  KSS_FM_DIV_RN_D,           /* div_rn_d, bits */
+  KSS_FM_LEAST_BF,           /* least_bf(requested a, capacity b) */
+  KSS_FM_ALLOC_D_LEAST,      /* alloc_score_d, LeastAllocated */
+  KSS_FM_ALLOC_D_MOST,       /* alloc_score_d, MostAllocated */
+  KSS_FM_DIV_I64,            /* div_i64<false> */
+  KSS_FM_DIV_F53,            /* div_f53 (a, b < 2^53) */
+  KSS_FM_QUOT_SMALL_I64,     /* quot_small_i64 */
+  KSS_FM_DIV_RN,             /* div_rn, bits */
+  KSS_FM_ALLOC_FAST_LEAST,   /* alloc_score_fast, LeastAllocated */
+  KSS_FM_ALLOC_FAST_MOST,    /* alloc_score_fast, MostAllocated */
+  KSS_FM_RCP_F32,            /* v_rcp_f32((float)b), bits: what small_div is given */
+  KSS_FM_RCP_F64,            /* 1.0 / (double)b, bits: what the others are given */
+  KSS_FM_NOPS
+};
+int kss_device_fastmath(int32_t device, int32_t op, const int64_t* a, const int64_t* b, int64_t* out, int32_t n);
 
 /* ---- synthetic clusters (SplitMix64, seed 0x5EED0000 + config) */
 typedef struct kss_synth {

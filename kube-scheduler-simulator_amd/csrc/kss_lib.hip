@@ -709,6 +709,36 @@ __global__ void k_go_log(const double* x, double* y, int n) {
   if (i < n) y[i] = go_log_dev(x[i]);
 }
 
+// Test support (kss_device_fastmath): one primitive of the exact-division set per element, with
+// the reciprocals formed as the scheduling kernels form them (v_rcp_f32 of the divisor for
+// small_div, the device's own f64 division 1.0 / (double)A for the rest).
+__global__ void k_fastmath_probe(int op, const int64_t* a, const int64_t* b, int64_t* out, int n) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int64_t ai = a[i], bi = b[i];
+  const double ad = (double)ai, bd = (double)bi;
+  const double inv = bi > 0 ? 1.0 / (double)bi : 0.0;
+  int64_t r = 0;
+  switch (op) {
+    case KSS_FM_SMALL_DIV: r = small_div((int32_t)ai, (int32_t)bi, __builtin_amdgcn_rcpf((float)(int32_t)bi)); break;
+    case KSS_FM_QUOT_SMALL_D: r = quot_small_d(ad, bd, inv); break;
+    case KSS_FM_DIV_RN_D: r = (int64_t)__double_as_longlong(div_rn_d(ad, bd, inv)); break;
+    case KSS_FM_LEAST_BF: r = least_bf(ad, bd, inv); break;
+    case KSS_FM_ALLOC_D_LEAST: r = alloc_score_d(KSS_FIT_LEAST_ALLOCATED, ad, bd, inv); break;
+    case KSS_FM_ALLOC_D_MOST: r = alloc_score_d(KSS_FIT_MOST_ALLOCATED, ad, bd, inv); break;
+    case KSS_FM_DIV_I64: r = div_i64<false>(ai, bi); break;
+    case KSS_FM_DIV_F53: r = div_f53(ai, bi); break;
+    case KSS_FM_QUOT_SMALL_I64: r = quot_small_i64(ai, bi, inv); break;
+    case KSS_FM_DIV_RN: r = (int64_t)__double_as_longlong(div_rn(ai, bi, inv)); break;
+    case KSS_FM_ALLOC_FAST_LEAST: r = alloc_score_fast(KSS_FIT_LEAST_ALLOCATED, ai, bi, inv); break;
+    case KSS_FM_ALLOC_FAST_MOST: r = alloc_score_fast(KSS_FIT_MOST_ALLOCATED, ai, bi, inv); break;
+    case KSS_FM_RCP_F32: r = (int64_t)__float_as_uint(__builtin_amdgcn_rcpf((float)(int32_t)bi)); break;
+    case KSS_FM_RCP_F64: r = (int64_t)__double_as_longlong(inv); break;
+    default: break;
+  }
+  out[i] = r;
+}
+
 // AssumePod / ForgetPod deltas of one pod, carried in the kernel arguments (no upload).
 struct CommitArgs {
   int64_t req[KSS_NRES];
@@ -6072,6 +6102,25 @@ int kss_device_go_log(int32_t device, const double* x, double* y, int32_t n) {
   hipLaunchKernelGGL(k_go_log, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d, d + n, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(y, d + n, 8 * (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int kss_device_fastmath(int32_t device, int32_t op, const int64_t* a, const int64_t* b, int64_t* out, int32_t n) {
+  if (!a || !b || !out || n < 0 || op < 0 || op >= KSS_FM_NOPS) return fail(KSS_E_INVAL, "bad arguments");
+  for (int32_t i = 0; i < n; i++)  // every primitive divides by b; small_div takes int32 operands
+    if (b[i] <= 0 || a[i] < 0 || ((op == KSS_FM_SMALL_DIV || op == KSS_FM_RCP_F32) && (a[i] > INT32_MAX || b[i] > INT32_MAX)))
+      return fail(KSS_E_INVAL, "fastmath probe: operand outside the primitive's domain");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(device));
+  int64_t* d = nullptr;
+  HIP_TRY(hipMalloc(&d, 24 * (size_t)n));
+  std::unique_ptr<int64_t, void (*)(int64_t*)> hold(d, [](int64_t* p) { hipFree(p); });
+  HIP_TRY(hipMemcpy(d, a, 8 * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d + n, b, 8 * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_fastmath_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, op, d, d + n,
+                     d + 2 * (size_t)n, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d + 2 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -89,6 +89,7 @@ SIGNATURES = [
     ("kss_last_simple_form", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_plan_shapes", C.c_int, [C.POINTER(abi.PodSet), C.c_int32, P(C.c_int32), P(C.c_int32)]),
     ("kss_device_go_log", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    ("kss_device_fastmath", C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     ("kss_plan_podset", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.c_void_p]),
     ("kss_plan_podset_ex", C.c_int, [C.POINTER(abi.Cluster), C.POINTER(abi.PodSet), C.POINTER(abi.Profile),
                                      C.c_void_p]),
@@ -828,6 +829,23 @@ def device_go_log(x, device: int = 0) -> np.ndarray:
     y = np.empty_like(x)
     check(lib().kss_device_go_log(device, x.ctypes.data, y.ctypes.data, len(x)))
     return y
+
+
+FASTMATH_OPS = ("small_div", "quot_small_d", "div_rn_d", "least_bf", "alloc_score_d_least", "alloc_score_d_most",
+                "div_i64", "div_f53", "quot_small_i64", "div_rn", "alloc_score_fast_least", "alloc_score_fast_most",
+                "rcp_f32", "rcp_f64")  # the KSS_FM_* codes of kss.h, in order
+
+
+def device_fastmath(op: str, a, b, device: int = 0) -> np.ndarray:
+    """One exact-division primitive at every (a[i], b[i]) as the scheduling kernels evaluate it on
+    the device (kss_device_fastmath): int64 operands, int64 results (the double- and float-valued
+    ops return bit patterns)."""
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    b = np.ascontiguousarray(b, dtype=np.int64)
+    assert a.shape == b.shape and a.ndim == 1
+    out = np.empty_like(a)
+    check(lib().kss_device_fastmath(device, FASTMATH_OPS.index(op), a.ctypes.data, b.ctypes.data, out.ctypes.data, len(a)))
+    return out
 
 
 def plan_shapes(podset: abi.PodSet, n_scalar: int = 0):

@@ -3,7 +3,8 @@
 divisions: integer floor quotients from a perturbed float reciprocal, int64 quotients from
 a double reciprocal, and the correctly rounded float64 quotient RN(a/b) from two FMA
 residual steps on RN(1/b) (Markstein).  tests/csrc/fastmath_check.c replays the device's
-operation sequence; the samples cover the operand ranges the device path admits."""
+operation sequence; the samples cover the operand ranges the device path admits.
+tests/test_gpu_fastmath.py runs the device's own functions and reciprocals on the GPU."""
 import os
 import shutil
 import subprocess
