@@ -1068,7 +1068,9 @@ struct kss_ctx {
   int last_kernel = 0;     // 0 k_schedule, 1 k_simple, 2 k_spread
   int meta_n = 0;          // pods with an outcome in meta_host
   bool small_values = false;  // every allocatable cpu/mem/eph < 2^46: k_simple's divisions stay below 2^53
-  F64Bounds f64_cluster, f64_pods;  // k_simple exactness bounds of the loaded snapshot / staged pods
+  F64Bounds f64_cluster, f64_pods;  // k_simple exactness bounds of the node state as it is now / staged pods
+  F64Bounds f64_cluster0;           // ... of the loaded snapshot (kss_reset_node_state)
+  std::vector<double> staged_creq, staged_cnz;  // per staged pod: its largest commit delta (f64_commit)
   bool axis_meta_dirty = false;  // meta_buf holds node-axis outcomes not yet copied to meta_host
   DevBuf axis_cv;
   int axis_max_blocks = 0;  // KSS_AXIS_BLOCKS: cap on the node-axis grid (tuning)
@@ -1334,7 +1336,11 @@ int validate(const kss_cluster* cl, const kss_podset* ps, int n) {
 // Cluster side: the largest snapshot Requested / NonZeroRequested (cpu, memory,
 // ephemeral); pod side: the largest request of any kind.  A node's Requested grows by
 // at most n_pods commits of the largest commit delta (a bound that holds even without
-// the NodeResourcesFit filter).
+// the NodeResourcesFit filter).  The cluster side is kept across a context's life: every
+// path that commits raises it by what it can have added (f64_commit: a batch by n_pods
+// times its largest delta, kss_commit / the service / the node axis by the pod's own),
+// kss_apply_node_delta by the rows it writes, and kss_reset_node_state puts the loaded
+// snapshot's values back.  It never falls otherwise (a rollback leaves it: an upper bound).
 void f64_bounds_cluster(const kss_cluster* cl, F64Bounds& b) {
   const size_t N = (size_t)cl->n_nodes;
   for (size_t i = 0; i < 3 * N; i++) {
@@ -1368,6 +1374,17 @@ bool f64_exact(const F64Bounds& c, const F64Bounds& p, int n_pods) {
   const double lim = 4503599627370496.0;  // 2^52: sums of two such values stay below 2^53
   return !c.neg && !p.neg && p.max_pod < lim && c.max_req0 + (double)n_pods * p.max_creq < lim &&
          c.max_nz0 + (double)n_pods * p.max_cnz < lim;
+}
+// Commits raised some node's Requested by at most `creq` and its NonZeroRequested by at most `cnz`.
+void f64_commit(F64Bounds& c, double creq, double cnz) {
+  c.max_req0 += std::max(creq, 0.0);
+  c.max_nz0 += std::max(cnz, 0.0);
+}
+void f64_commit_pod(F64Bounds& c, const kss_pod& p) {
+  double creq = 0, cnz = 0;
+  for (int r = 0; r < 3; r++) creq = std::max(creq, (double)p.commit_req[r]);
+  for (int r = 0; r < 2; r++) cnz = std::max(cnz, (double)p.commit_nz[r]);
+  f64_commit(c, creq, cnz);
 }
 
 // A pod of the ports-and-images form (k_simple_pi): host ports or node-cached images.
@@ -2417,6 +2434,7 @@ int kss_load_cluster(kss_ctx* ctx, const kss_cluster* cl) {
     ctx->small_values = small;
     ctx->f64_cluster = F64Bounds{};
     f64_bounds_cluster(cl, ctx->f64_cluster);
+    ctx->f64_cluster0 = ctx->f64_cluster;
   }
   ctx->key_card_h.assign(cl->key_card, cl->key_card + cl->n_label_keys);
   ctx->key_flags_h.assign(cl->key_flags, cl->key_flags + cl->n_label_keys);
@@ -2528,6 +2546,15 @@ static int axis_check(kss_ctx* ctx, int32_t pod_index) {
   return ctx->axis_cv.ensure(sizeof(int32_t) * 5 * (size_t)std::max(ctx->dc.N, 1));
 }
 
+// A node-axis commit (k_axis_eval's pending commit, k_axis_commit) may have landed on one of this
+// context's rows: the value and count bounds of the fast batch kernels follow it as they follow kss_commit.
+static void axis_commit_bounds(kss_ctx* ctx, int32_t pod_index) {
+  f64_commit(ctx->f64_cluster, ctx->staged_creq[(size_t)pod_index], ctx->staged_cnz[(size_t)pod_index]);
+  const double own = pod_index < (int)ctx->staged_bp.size() ? (double)ctx->staged_bp[(size_t)pod_index].tlen : 0.0;
+  ctx->count_bound += 1.0 + own;
+  ctx->cell_bound += 1.0 + own;
+}
+
 static dim3 axis_grid(kss_ctx* ctx) {
   const int blocks = (ctx->dc.N + AXIS_THREADS - 1) / AXIS_THREADS;
   return dim3((unsigned)std::max(1, std::min(blocks, ctx->axis_max_blocks > 0 ? ctx->axis_max_blocks : 4 * ctx->n_cu)));
@@ -2552,9 +2579,10 @@ int kss_axis_eval(kss_ctx* ctx, int32_t pod_index, int64_t* stats_dev, const int
                      (const long long*)prev_gathered_dev, world, (long long*)key_zero_dev, chosen_dev,
                      (PodMeta*)ctx->meta_buf.p, ctx->axis_no_fold);
   HIP_TRY(hipGetLastError());
-  if (prev_key_dev) {
+  if (prev_key_dev) {  // this launch commits the previous pod first
     ctx->meta_n = std::max(ctx->meta_n, (int)pod_index);
     ctx->axis_meta_dirty = true;
+    axis_commit_bounds(ctx, pod_index - 1);
   }
   return 0;
 }
@@ -2590,6 +2618,7 @@ int kss_axis_commit(kss_ctx* ctx, int32_t pod_index, const int64_t* key_dev, con
   HIP_TRY(hipGetLastError());
   ctx->meta_n = std::max(ctx->meta_n, pod_index + 1);
   ctx->axis_meta_dirty = true;
+  axis_commit_bounds(ctx, pod_index);
   return 0;
 }
 
@@ -2603,6 +2632,7 @@ int kss_reset_node_state(kss_ctx* ctx) {
                          ctx->dc.pv_owner,   ctx->dc.claim_node};
   ctx->count_bound = ctx->count_bound0;
   ctx->cell_bound = ctx->cell_bound0;
+  ctx->f64_cluster = ctx->f64_cluster0;  // the rows are the snapshot's again (commits and deltas gone)
   ctx->bound_log.clear();
   ctx->bound_dirty = true;
   ctx->state_unknown = false;
@@ -4100,6 +4130,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (errw && commit) {  // bounds as if every pod committed (upper bounds stay safe); log unknown
     ctx->count_bound = count_total;
     ctx->cell_bound = std::max(ctx->cell_bound, cell_total);
+    f64_commit(ctx->f64_cluster, (double)n * ctx->f64_pods.max_creq, (double)n * ctx->f64_pods.max_cnz);
     ctx->state_unknown = true;
   }
   if (errw == 2)
@@ -4109,6 +4140,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   if (commit) {
     ctx->count_bound = count_total;
     ctx->cell_bound = std::max(ctx->cell_bound, cell_total);
+    f64_commit(ctx->f64_cluster, (double)n * ctx->f64_pods.max_creq, (double)n * ctx->f64_pods.max_cnz);
   }
   ctx->meta_host.resize((size_t)std::max(n, 1));
   std::memcpy(ctx->meta_host.data(), hb + o_meta, mb);
@@ -4163,6 +4195,14 @@ static int vol_pack_state(kss_ctx* ctx, bool& fits) {
 static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   ctx->f64_pods = F64Bounds{};
   f64_bounds_pods(ps, ctx->f64_pods);
+  ctx->staged_creq.assign((size_t)ps->n_pods, 0.0);
+  ctx->staged_cnz.assign((size_t)ps->n_pods, 0.0);
+  for (int i = 0; i < ps->n_pods; i++) {
+    F64Bounds one;
+    f64_commit_pod(one, ps->pods[i]);
+    ctx->staged_creq[(size_t)i] = one.max_req0;
+    ctx->staged_cnz[(size_t)i] = one.max_nz0;
+  }
   ctx->staged_max_own = 0;
   ctx->staged_names = false;
   for (int i = 0; i < ps->n_pods; i++) {
@@ -4561,6 +4601,7 @@ static int commit_one(kss_ctx* ctx, const kss_podset* ps, int32_t pod_index, int
   if (sign > 0) {
     ctx->count_bound += 1.0 + (double)p.own_terms_len;
     ctx->cell_bound += 1.0 + (double)p.own_terms_len;
+    f64_commit_pod(ctx->f64_cluster, p);
   }
   hipLaunchKernelGGL(k_commit, dim3(1), dim3(64), 0, ctx->stream, ctx->dc, a);
   HIP_TRY(hipGetLastError());  // no synchronisation: every later call on the ctx stream is ordered after it
@@ -5115,6 +5156,7 @@ static int svc_commit(kss_ctx* ctx, int32_t pod_index, int32_t node, int sign) {
     const double own = pod_index < (int)ctx->staged_bp.size() ? (double)ctx->staged_bp[pod_index].tlen : 0.0;
     ctx->count_bound += 1.0 + own;
     ctx->cell_bound += 1.0 + own;
+    f64_commit(ctx->f64_cluster, ctx->staged_creq[(size_t)pod_index], ctx->staged_cnz[(size_t)pod_index]);
   }
   if (sign > 0 && pod_index < (int)ctx->staged_uid.size()) {
     // assume -> SchedulingQueue.DeleteNominatedPodIfExists, as kss_commit (the grid clears the

@@ -270,3 +270,42 @@ def test_contests_tie_in_exact_arithmetic():
             assert cc.node_names[ch[j]] == want and res.meta(j)["scored"] == 1, (pname, j, e)
             assert want == e["names"][0] or not tie
         assert ties["est_low"] >= 8 and ties["est_high"] >= 8, (pname, ties)
+
+
+# --------------------------------------------------------------------------------------
+# the fixtures of tests/test_gpu_bounds_lifetime.py hold what they claim
+# --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("batches", [1, 2])
+def test_lifetime_cases_cross_the_sum_bound_after_one_batch(batches):
+    """lifetime_cases(batches=1): after one batch the largest NonZeroRequested plus n * max commit is
+    across 2^52 (the best-effort pods landed on the near-bound nodes); with batches=2 even the load-time
+    maximum plus two batches' n * max commit stays inside."""
+    cases = vx.lifetime_cases(N_PAIRS, batches)
+    cc, cp, _ = compile_cluster(*vx.twin_cluster(cases))
+    n, creq, cnz = cp.n, int(cp.pods["commit_req"][:, :3].max()), int(cp.pods["commit_nz"].max())
+    N = cc.n_nodes
+    load = (int(cc.arrays["requested"][:3, :N].max()), int(cc.arrays["nonzero"][:, :N].max()))
+    assert (load[0] + batches * n * creq, load[1] + batches * n * cnz) == vx.f64_sum(cases, batches * n) == (vx.E52 - 1, vx.E52 - 1)
+    _, _, fin = oracle(cc, cp, abi.default_profile())
+    after = (int(fin["requested"][:3, :N].max()), int(fin["nonzero"][:, :N].max()))
+    assert after[1] > load[1] and after[0] == load[0]
+    assert (after[1] + n * cnz >= vx.E52) == (batches == 1)
+
+
+def test_witness_passes_2_53_on_an_odd_value():
+    """Five copies of the witness pod, without the NodeResourcesFit filter: all land on a000, and the
+    oracle's int64 Requested equals the Python-integer sum after each (odd and above 2^53 after four)."""
+    nodes, bound, pods = vx.twin_cluster(vx.witness_cases())
+    five = pods + [p for k in range(1, 5) for p in vx.renamed(pods, "-%d" % k)]
+    cc, cp, _ = compile_cluster(nodes, bound, five)
+    prof = abi.default_profile()
+    prof.filter_enabled &= ~(1 << abi.KSS_F_NODE_RESOURCES_FIT)
+    a = cc.node_names.index("a000")
+    for runs in range(1, 6):
+        ch, _, fin = oracle_c.schedule(prof, cc.as_struct(), cp.as_struct(), runs, cc.n_nodes, record="meta")
+        assert list(ch) == [a] * runs
+        assert int(fin["requested"][0, a]) == vx.witness_requested(runs)
+    assert vx.witness_requested(1) + vx.WITNESS_POD >= vx.E52 > vx.witness_requested(1)
+    assert float(vx.witness_requested(4)) != vx.witness_requested(4)  # no double holds it
+    # with the filter on, the pod fits nowhere: the bound is all that keeps the fast kernels off these sums
+    assert list(oracle(cc, cp, abi.default_profile())[0]) == [-1] * 5

@@ -502,6 +502,49 @@ def f64_sum(cases, n_pods):
     return mreq + n_pods * creq, mnz + n_pods * cnz
 
 
+def lifetime_cases(n_pairs=64, batches=1):
+    """make_cases whose near-bound operands are computed for `batches` batches of one pod per pair on
+    one context: max Requested + batches * n_pairs * max commit = 2^52 - 1 (and the same for
+    NonZeroRequested).  batches=1 is bound_cases' sum-in.  The best-effort pods of the near-bound
+    pairs do land there and raise NonZeroRequested by the defaults, so after one batch the true
+    maximum plus n_pairs * max commit is across 2^52 for batches=1 and inside it for batches=2."""
+    cases = make_cases(n_pairs, n_pods_bound=batches * n_pairs)
+    assert f64_sum(cases, batches * n_pairs) == (E52 - 1, E52 - 1)
+    return cases
+
+
+def renamed(pods, suffix):
+    """Copies of pods under other names (a second batch of the same shapes)."""
+    out = []
+    for p in pods:
+        q = dict(p)
+        q["metadata"] = dict(p["metadata"], name=p["metadata"]["name"] + suffix)
+        out.append(q)
+    return out
+
+
+# The wrong-value witness: one pair whose cpu Requested is odd and near 2^51 on nodes far too small for
+# it, and one pod whose cpu request is odd and near 2^51.  Under a profile without the
+# NodeResourcesFit filter the pod lands on a<0> every time; Requested + commit is 2^52 - 2 for the
+# first pod (inside the sum bound) and passes 2^53 on an odd value with the fourth.
+WITNESS_REQ, WITNESS_POD = (1 << 51) - 3, (1 << 51) + 1
+
+
+def witness_cases():
+    ops = [(E46 - 1, WITNESS_REQ + WITNESS_POD), (E46 - 1, 1000 + 7), (E46 - 1, 3 + 3)]
+    cases = [_case("witness", ops, (WITNESS_POD, 7, 3))]
+    assert f64_sum(cases, 1) == (E52 - 2, E52 - 2)
+    return cases
+
+
+def witness_requested(runs):
+    """cpu Requested of a<0> after `runs` one-pod batches, in Python integers."""
+    return WITNESS_REQ + runs * WITNESS_POD
+
+
+assert witness_requested(4) > E53 and witness_requested(4) % 2 == 1
+
+
 def request_bound_cases(inside):
     """One empty pair and one pod whose memory request is 2^52 - 1 (inside) or 2^52 (across).  Only a
     batch of one pod on nodes without bound pods keeps the sum bound beside such a request; the pod
