@@ -489,8 +489,19 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * (KSS_VOL_BIND_WFFC), the cluster has at most 64 volume rows and 8 attach-limit keys, every shared
  * KSS_VOL_LIMIT entry names its row's key, and per key the largest attached count plus everything
  * the batch can add, and every limit, stay below 65535; a batch under percentageOfNodesToScore <
- * 100, the shape table, k_spread, sweeps, split grids and the service grid do not take such pods;
- * a batch without a volume program is routed and launched as with 0; kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
+ * 100 (see "simple_volumes_window"), the shape table, k_spread, sweeps, split grids and the service
+ * grid do not take such pods; a batch without a volume program is routed and launched as with 0;
+ * kss_plan_podset follows it),
+ * "simple_volumes_window" (default 0; effective only with "simple_ports_images" 1 and
+ * "simple_volumes" 1: a batch of the volumes form whose search is windowed --
+ * percentageOfNodesToScore below 100, 0 being the adaptive window, on a node list long enough to
+ * stop early -- runs that form's window kernels on k_simple instead of staying on k_schedule, under
+ * every other condition of the form and the window's own, no pod with a PreFilterResult node list;
+ * nextStartNodeIndex and the volume state are left as k_schedule leaves them; with 0 such a batch
+ * is routed as before the option existed; kss_plan_podset_ex follows it),
+ * "sweep_volumes" (default 0; effective only with "sweep_ports_images" 1: a scenario sweep whose pods
+ * hold volume programs is staged instead of refused -- see kss_sweep_create; a sweep without such a
+ * pod is staged and launched as with 0; kss_plan_sweep follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -740,23 +751,44 @@ int kss_schedule_scenarios(int32_t device, const kss_profile* prof, int32_t n_sc
  * k_static_pi + k_simple_pi_sweep (kernel 1) when every scenario meets k_simple's conditions and
  * every pod's positive preferred NodeAffinity weights sum to at most 8191, else on k_schedule
  * (kernel 0).  A sweep without such a pod keeps its layout, upload_bytes and kernels whatever
- * the option says.  A pod with a volume program refuses the sweep with either value. */
+ * the option says.
+ *
+ * Pods with a volume program: refused (KSS_E_UNSUPPORTED) with either value of "sweep_ports_images"
+ * unless the option "sweep_volumes" is 1 as well (it is effective only with "sweep_ports_images" 1).
+ * With both 1, a scenario with an unbound WaitForFirstConsumer claim (KSS_VOL_BIND_WFFC) still refuses
+ * the sweep (the binder's assume cache is not packed for sweeps); otherwise a sweep in which some
+ * scenario holds a volume pod packs every scenario's volume columns (kss_sweep_form 2).  It runs in
+ * the volumes form -- k_static_pi + k_static_vol + k_simple_vol_sweep, kernel 1 -- when every
+ * scenario has at most 64 volume rows and 8 attach-limit keys, every shared KSS_VOL_LIMIT entry
+ * names its row's key, no 16-bit counter can overflow on the scenario's own vol_attached /
+ * vol_limit, and the sweep meets k_simple's sweep conditions; its workgroup is the largest multiple
+ * of 64 lanes, at most the usual preference, whose two node slots per lane fit the form's LDS (384
+ * lanes, 768 nodes).  Every scenario's used-rows and attached columns are mutable state, packed on
+ * the host and restored by every kss_sweep_run; the limit columns and the pods' records are inputs.
+ * Else -- a scenario outside those limits (the reason names it), the window, a scenario of more than
+ * 768 nodes -- the whole sweep runs on k_schedule (kernel 0) over vol_count / vol_attached /
+ * vol_limit packed as they are.  A sweep without a volume pod keeps its layout, upload_bytes and
+ * kernels whatever "sweep_volumes" says. */
 typedef struct kss_sweep kss_sweep;
 kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_scen, const kss_cluster* clusters,
                             const kss_podset* podsets);
 int kss_sweep_run(kss_sweep* sw, int32_t* chosen_out, double* device_ms);
 int kss_sweep_info(kss_sweep* sw, double* stage_ms, int32_t* kernel, int64_t* upload_bytes);
-/* 1 when the sweep runs in the ports-and-images form, 0 otherwise; <0 on error */
+/* 1 when the sweep runs in the ports-and-images form, 2 when it also packs volume columns (some pod
+ * holds a volume program, option "sweep_volumes"; with kernel 1: the volumes form), 0 otherwise;
+ * <0 on error */
 int kss_sweep_form(kss_sweep* sw);
 void kss_sweep_destroy(kss_sweep* sw);
 /* Host only (no device): the routing kss_sweep_create would choose for these scenarios under
- * `prof` and the process-wide option "sweep_ports_images" -- the same function decides both.
- * out[0] = kernel (1 the k_simple family, 0 k_schedule), out[1] = 1 the ports-and-images form,
+ * `prof` and the process-wide options "sweep_ports_images" and "sweep_volumes" -- the same function
+ * decides both.  out[0] = kernel (1 the k_simple family, 0 k_schedule), out[1] = 1 the
+ * ports-and-images form, 2 with volume columns as well (kss_sweep_form),
  * out[2], out[3] = the first scenario and pod that keep the sweep off the k_simple family or refuse
  * it (-1: none, or no single one).  Returns the reason code (>= 0: kss_plan_reason; 0 eligible),
  * or a negative KSS_E_* exactly where kss_sweep_create would fail: KSS_E_UNSUPPORTED for a pod with
- * a volume program (either option value) and for a pod with host ports or image rows with the
- * option 0 (kss_last_error names which; out[2], out[3] name the pod). */
+ * a volume program (unless both options are 1; then only for a WaitForFirstConsumer claim) and for a
+ * pod with host ports or image rows with "sweep_ports_images" 0 (kss_last_error names which; out[2],
+ * out[3] name the pod). */
 int kss_plan_sweep(const kss_profile* prof, int32_t n_scen, const kss_cluster* clusters, const kss_podset* podsets,
                    int32_t out[4]);
 
@@ -895,7 +927,8 @@ int kss_last_simple_exchange(kss_ctx* ctx, int32_t* out2);
 /* The form of k_simple the last run took: out2[0] = 1 when it ran the volumes form (option
  * "simple_volumes": pods with volume programs; the volume filters on a used-rows word and packed
  * attach counters per node in LDS), else 0; out2[1] = the loop kernel's dynamic LDS bytes per
- * workgroup (0 when the last run was not on k_simple).  kss_last_kernel stays 1. */
+ * workgroup (0 when the last run was not on k_simple).  kss_last_kernel stays 1.  A windowed batch
+ * that ran the form's window kernels (option "simple_volumes_window") is reported the same way. */
 int kss_last_simple_form(kss_ctx* ctx, int32_t* out2);
 /* kernel of the last scheduling launch: 0 general (k_schedule), 1 compact (k_simple:
  * batches without spread / inter-pod programs and without a record), 2 k_spread (batches

@@ -31,6 +31,8 @@
 //                with volume programs; a used-rows word and packed attach counters per node in
 //                LDS, VolumeBinding / VolumeZone in the static word (k_static_vol), the columns
 //                packed / written back around the batch (k_vol_pack, k_vol_unpack, k_vol_counts).
+//                k_simple_vol<.., WIN = true> runs the percentageOfNodesToScore window (option
+//                simple_volumes_window).
 //   k_spread    the sequential loop of batches WITH spread / inter-pod-affinity programs
 //                (no result record): node rows, label ids, the pod's count rows and
 //                the launch's commits in LDS, host-resolved pod programs (GPod),
@@ -86,7 +88,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_SIMPLE_VOL, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_SIMPLE_VOL, O_SIMPLE_VOL_WIN, O_SWEEP_VOL, O_N
 };
 struct OptDef {
   const char* name;
@@ -130,6 +132,8 @@ const OptDef kOptDefs[O_N] = {
     {"service_ports_images", "KSS_SERVICE_PORTS_IMAGES", 0},  // the service grid's k_simple-shaped chain for such pods (independent of the three above)
     {"sweep_ports_images", "KSS_SWEEP_PORTS_IMAGES", 0},  // scenario sweeps admit such pods: k_simple_pi_sweep or k_schedule (independent of the four above)
     {"simple_volumes", "KSS_SIMPLE_VOLUMES", 0},  // k_simple's volumes form for pods with volume programs (effective only with simple_ports_images 1)
+    {"simple_volumes_window", "KSS_SIMPLE_VOLUMES_WINDOW", 0},  // that form under the percentageOfNodesToScore window (effective only with the two above)
+    {"sweep_volumes", "KSS_SWEEP_VOLUMES", 0},  // scenario sweeps admit pods with volume programs: k_simple_vol_sweep or k_schedule (effective only with sweep_ports_images 1)
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -352,7 +356,7 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple(const DevJob* __rest
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
   const int Wl = X.n > 1 ? X.wl : W;  // shards of this launch (a split grid runs [w_off, w_off + wl))
   // (an XCD-local grid's counters: behind the granules, and the window's cut granules)
-  auto ctr_off = [&] { return WIN ? 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 : 2 * (size_t)W * SX_VALS; };
+  auto ctr_off = [&] { return xcd_ctr_off<WIN>(W); };
   int xs = 0;  // one cluster, every shard on XCD 0; the other workgroups leave
   if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, ctr_off, W, err)) < 0) return;
   const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_pi(const DevJob* __r
   extern __shared__ __attribute__((aligned(16))) long long smem[];
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
   const int Wl = X.n > 1 ? X.wl : W;
-  auto ctr_off = [&] { return WIN ? 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 : 2 * (size_t)W * SX_VALS; };
+  auto ctr_off = [&] { return xcd_ctr_off<WIN>(W); };
   int xs = 0;  // as k_simple
   if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, ctr_off, W, err)) < 0) return;
   const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
@@ -503,11 +507,12 @@ __global__ void k_handoff_final_pi(const DevJob* __restrict__ jobs, int W, int w
 static const void* spread_pi_fn(bool def, bool lb, bool win);
 // ... and k_simple_pi_sweep<DEF>, the ports-and-images form of a scenario sweep, behind those
 static const void* simple_pi_sweep_fn(bool def);
-// ... and the volumes form of k_simple (option simple_volumes), behind those: k_simple_vol<DEF>, the
+// ... and the volumes form of k_simple (option simple_volumes), behind those: k_simple_vol<DEF, WIN>, the
 // static verdicts (k_static_vol) and the node-state columns' pack / write-back kernels
-static const void* simple_vol_fn(bool def);
+static const void* simple_vol_fn(bool def, bool win);
+static const void* simple_vol_sweep_fn(bool def);
 static void launch_static_vol(hipStream_t st, const DevJob* jobs, const kss_profile& pr, int k0, int k1, int n_lo, int n_hi,
-                              const SVolLaunch* vl);
+                              const SVolLaunch* vl, int n_jobs = 1);
 static void launch_vol_writeback(hipStream_t st, const DevJob* jobs, int n_nodes, int n_pods, const SVolLaunch* vl);
 static int vol_pack_state(kss_ctx* ctx, bool& fits);
 // The form's launch block on the device (kss_ctx::vol_state_buf): SVolLaunch, the maxima k_vol_pack
@@ -1029,7 +1034,8 @@ struct kss_ctx {
   DevBuf sport_buf;
   std::vector<SPort> sport_host;
   // its volumes form (option simple_volumes): the staged batch holds a pod with a volume program
-  // and vol_form_admit took it (k_simple_vol, one part, no window); the pods' SVol records, what
+  // and vol_form_admit took it (k_simple_vol, one part; the percentageOfNodesToScore window only
+  // with the option simple_volumes_window); the pods' SVol records, what
   // their commits can add per limit key (condition 4 is checked at run time against the device's
   // columns), and the launch's block: SVolLaunch, the packed node-state columns, the maxima
   bool spod_vol = false;
@@ -1477,7 +1483,14 @@ bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int
     form = force;
     if (opt(O_SIMPLE_PI) || (svc && opt(O_SERVICE_PI)))
       for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
-    if (va && !force && opt(O_SIMPLE_PI) && opt(O_SIMPLE_VOL)) {
+    if (va && force) {  // a scenario of a sweep in the volumes form (sweep_plan): records of the form whatever the
+                        // options say; a scenario without a volume pod gets zero records
+      bool any = false;
+      for (int i = 0; i < ps->n_pods; i++) any |= ps->pods[i].vol_len > 0;
+      if (any && !vol_form_admit(ps, *va, *pi)) return false;  // (pi->vol_code, pi->vol_pod: why)
+      if (!any) pi->vols.assign((size_t)std::max(ps->n_pods, 1), SVol{});
+      pi->vol = vol = true;
+    } else if (va && opt(O_SIMPLE_PI) && opt(O_SIMPLE_VOL)) {
       bool any = false;
       for (int i = 0; i < ps->n_pods; i++) any |= ps->pods[i].vol_len > 0;
       vol = any && vol_form_admit(ps, *va, *pi);
@@ -3378,10 +3391,15 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
                          const int32_t* pod_off = nullptr, const SVolLaunch* vl = nullptr) {
   // the volumes form (one job; vl: the launch block on the device, vol_pack_state): k_static_pi +
   // k_static_vol + k_simple_vol per chunk, then the packed attached counts back into vol_attached
-  // and the pods' own rows into vol_count (k_vol_unpack, k_vol_counts).  No table, no window, no split.
-  const bool vol = vl != nullptr;
-  if (vol && (!sports || pod_off || n_shapes > 0 || k_find > 0 || split || n_jobs != 1 || st2))
-    return fail(KSS_E_INVAL, "volumes form: one job of the ports-and-images form, no table, window or split");
+  // and the pods' own rows into vol_count (k_vol_unpack, k_vol_counts).  No table, no split; the
+  // window (k_find > 0) as the ports-and-images form runs it (the caller checked simple_volumes_window).
+  // ... of a sweep (many jobs; pod_off as in the ports-and-images sweep, vl: SVolLaunch[n_jobs], each with
+  // its scenario's columns and records): k_static_pi + k_static_vol over every job + k_simple_vol_sweep;
+  // the columns are the sweep's own mutable state, so nothing is written back.
+  const bool vol = vl != nullptr, vol_sweep = vol && pod_off != nullptr;
+  if (vol && !vol_sweep && (!sports || n_shapes > 0 || split || n_jobs != 1 || st2))
+    return fail(KSS_E_INVAL, "volumes form: one job of the ports-and-images form, no table or split");
+  if (vol_sweep && (!sports || st2)) return fail(KSS_E_INVAL, "sweep volumes form: the ports-and-images sweep, one stream");
   // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
   // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
   const bool pi = sports != nullptr;
@@ -3410,8 +3428,9 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
   if (flat && gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
     return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
-  const void* fn = pi_sweep ? simple_pi_sweep_fn(def)
-                   : vol   ? simple_vol_fn(def)
+  const void* fn = vol_sweep ? simple_vol_sweep_fn(def)
+                   : pi_sweep ? simple_pi_sweep_fn(def)
+                   : vol   ? simple_vol_fn(def, win)
                    : flat  ? (pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat)
                    : tab ? (pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab)
                    : pi  ? (win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
@@ -3460,7 +3479,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
       launch_static(st, def, jobs, pr, n_jobs, k0, k1, n_lo, n_hi, max_keys, 0, pi);
       HIP_TRY(hipGetLastError());
       if (vol) {  // VolumeBinding / VolumeZone verdicts into the words just written
-        launch_static_vol(st, jobs, pr, k0, k1, n_lo, n_hi, vl);
+        launch_static_vol(st, jobs, pr, k0, k1, n_lo, n_hi, vl, n_jobs);
         HIP_TRY(hipGetLastError());
       }
     }
@@ -3475,7 +3494,8 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     unsigned long long* sp = k0 == 0 ? stamps : nullptr;
     void* args[] = {(void*)&jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
                     (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg,
-                    (void*)&sports, vol ? (void*)&vl : (void*)&pod_off};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's / k_simple_vol's two; the other kernels take 13)
+                    (void*)&sports, vol && !vol_sweep ? (void*)&vl : (void*)&pod_off,
+                    (void*)&vl};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's / k_simple_vol's two, k_simple_vol_sweep's three; the other kernels take 13)
     const int ci = k0 / chunk;
     if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
     if (xcd) {
@@ -3503,7 +3523,7 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
   hipLaunchKernelGGL(k_counts, dim3((unsigned)((n_pods_max + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, jobs, 0,
                      n_pods_max);
   HIP_TRY(hipGetLastError());
-  if (vol) {
+  if (vol && !vol_sweep) {
     launch_vol_writeback(st, jobs, max_nodes, n_pods_max, vl);
     HIP_TRY(hipGetLastError());
   }
@@ -3757,8 +3777,8 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
                    !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
                    // the ports-and-images form: one part, and the option still on (it is process-wide)
                    (!ctx->spod_pi || (!split && opt(O_SIMPLE_PI))) &&
-                   // its volumes form: that option too, and no window (no WIN instantiation)
-                   (!ctx->spod_vol || (opt(O_SIMPLE_VOL) && !(window && k_find < (int)N)));
+                   // its volumes form: that option too, and the window only with simple_volumes_window
+                   (!ctx->spod_vol || (opt(O_SIMPLE_VOL) && (opt(O_SIMPLE_VOL_WIN) || !(window && k_find < (int)N))));
   // ... and the packed fields cannot overflow (vol_form_admit's condition 4) on the columns as they
   // are now: packed here, before the batch's first launch
   if (simple_ok && ctx->spod_vol) {
@@ -5365,8 +5385,10 @@ struct Packer {
 // The read-only part of one scenario: cluster columns except the mutable ones, the pod
 // programs and (simple sweeps) the compact pod records.  pi (a sweep in the ports-and-images form):
 // + the image-score rows.
+// vol (a sweep whose pods hold volume programs, option sweep_volumes): + the volume limits, the row /
+// key dictionaries and the pods' volume entries, which k_schedule and k_static_vol read.
 void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const std::vector<SPod>* spods, DevJob& j,
-                 bool pi = false) {
+                 bool pi = false, bool vol = false) {
   const size_t N = (size_t)cl->n_nodes, K = (size_t)cl->n_label_keys;
   DevCluster& c = j.c;
   c.N = cl->n_nodes;
@@ -5403,10 +5425,18 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
     c.image_score = P.put(cl->image_score, (size_t)cl->n_images * N);
     c.n_images = cl->n_images;
   }
-  c.n_vol_rows = c.n_vol_keys = 0;  // sweeps refuse pods with volume programs (sweep_plan)
+  c.n_vol_rows = c.n_vol_keys = 0;  // without the option sweep_volumes sweeps refuse pods with volume programs (sweep_plan)
   c.vol_count = c.vol_attached = nullptr;
   c.vol_limit = c.vol_row_key = c.vol_key_plugin = nullptr;
   j.P.vols = nullptr;
+  if (vol) {
+    c.n_vol_rows = cl->n_vol_rows;
+    c.n_vol_keys = cl->n_vol_keys;
+    c.vol_limit = P.put(cl->vol_limit, (size_t)cl->n_vol_keys * N);
+    c.vol_row_key = P.put(cl->vol_row_key, (size_t)cl->n_vol_rows);
+    c.vol_key_plugin = P.put(cl->vol_key_plugin, (size_t)cl->n_vol_keys);
+    j.P.vols = P.put(ps->vols, (size_t)ps->n_vols);
+  }
   j.P.pods = P.put(ps->pods, (size_t)ps->n_pods);
   j.P.reqs = P.put(ps->reqs, (size_t)ps->n_reqs);
   j.P.terms = P.put(ps->terms, (size_t)ps->n_terms);
@@ -5419,7 +5449,8 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
 // The mutable columns of one scenario (AssumePod targets): the host image holds the
 // snapshot (the device's pristine copy); the device pointers address the live copy.  pi: + the
 // UsedPorts column (zero without a port dictionary), restored with the rest on every run.
-void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j, bool pi = false) {
+// vol: + vol_count / vol_attached (k_schedule's AssumePod targets).
+void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j, bool pi = false, bool vol = false) {
   const size_t N = (size_t)cl->n_nodes;
   j.c.requested = P.put(cl->requested, KSS_NRES * N);
   j.c.nonzero = P.put(cl->nonzero, 2 * N);
@@ -5427,6 +5458,49 @@ void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j, bool pi = false) 
   j.c.class_count = P.put(cl->class_count, (size_t)cl->n_classes * N);
   j.c.term_count = P.put(cl->term_count, (size_t)cl->n_terms * N);
   if (pi) j.c.port_used = P.put<uint64_t>(cl->n_ports > 0 ? cl->port_used : nullptr, N);
+  if (vol) {
+    j.c.vol_count = P.put(cl->vol_count, (size_t)cl->n_vol_rows * N);
+    j.c.vol_attached = P.put(cl->vol_attached, (size_t)cl->n_vol_keys * N);
+  }
+}
+
+// The volumes form's node-state columns of one scenario, packed on the host as k_vol_pack packs
+// them on the device (bit r of used = vol_count[r] > 0; key k's attached count / limit in word k / 4
+// at bit 16 (k % 4), a limit below 0 as SV_UNCHECKED).  sweep_plan admitted the scenario: at most
+// SV_ROWS rows, SV_KEYS keys, every value within a field.
+void vol_pack_host(const kss_cluster* cl, uint64_t* used, uint64_t* att, uint64_t* lim) {
+  const size_t N = (size_t)cl->n_nodes;
+  for (size_t n = 0; n < N; n++) {
+    uint64_t u = 0, a[2] = {0, 0}, l[2] = {0, 0};
+    for (int r = 0; r < cl->n_vol_rows && r < SV_ROWS; r++) u |= cl->vol_count[(size_t)r * N + n] > 0 ? 1ull << r : 0ull;
+    for (int k = 0; k < cl->n_vol_keys && k < SV_KEYS; k++) {
+      const int32_t av = cl->vol_attached[(size_t)k * N + n], lv = cl->vol_limit[(size_t)k * N + n];
+      const uint64_t af = (uint64_t)std::min(std::max(av, 0), (int32_t)SV_FIELD_MAX);
+      const uint64_t lf = lv < 0 ? (uint64_t)SV_UNCHECKED : (uint64_t)std::min(lv, (int32_t)SV_FIELD_MAX);
+      a[k >> 2] |= af << (16 * (k & 3));
+      l[k >> 2] |= lf << (16 * (k & 3));
+    }
+    if (used) used[n] = u;
+    if (att) att[n] = a[0], att[N + n] = a[1];
+    if (lim) lim[n] = l[0], lim[N + n] = l[1];
+  }
+}
+
+// The launch constants of one scenario (vol_pack_state's, from the scenario's own dictionaries).
+SVolLaunch vol_launch_consts(const kss_cluster* cl, const kss_profile& prof) {
+  SVolLaunch K{};
+  const uint32_t en = prof.filter_enabled;
+  for (int r = 0; r < cl->n_vol_rows && r < SV_ROWS; r++) {
+    const int k = cl->vol_row_key[r];
+    if (k >= 0 && k < SV_KEYS) K.keyrows[k] |= 1ull << r;
+  }
+  for (int k = 0; k < cl->n_vol_keys && k < SV_KEYS; k++) {
+    const int pl = cl->vol_key_plugin[k];
+    if ((en >> pl) & 1u) K.key_on |= 1u << k;
+    if (pl == KSS_F_NODE_VOLUME_LIMITS) K.key_csi |= 1u << k;
+  }
+  K.vr_on = (en >> KSS_F_VOLUME_RESTRICTIONS) & 1u;
+  return K;
 }
 
 }  // namespace
@@ -5448,6 +5522,8 @@ struct kss_sweep {
   bool simple = false;
   bool form = false;  // the ports-and-images form (option sweep_ports_images): both columns packed
   size_t sports_off = 0, podoff_off = 0;  // form on the k_simple family: SPort[total_pods + RING], int32[n_scen]
+  bool vform = false;     // some pod holds a volume program (option sweep_volumes): the volume columns packed
+  size_t vls_off = 0;     // ... on the k_simple family (the volumes form): SVolLaunch[n_scen]
   int chunk = 0;
   Geometry g;
   PlanNeeds need;
@@ -5467,8 +5543,12 @@ extern "C" {
 
 // The routing of a whole sweep (kss_plan_sweep and kss_sweep_create: one function, so the two
 // cannot disagree).  One launch serves every scenario, so the kernel and the form are one decision:
-//   - a pod with a volume program refuses the sweep (pack_inputs zeroes the volume columns), and so
-//     does a pod with host ports or image rows while the option sweep_ports_images is 0;
+//   - a pod with a volume program refuses the sweep unless the options sweep_ports_images and
+//     sweep_volumes are both on (then only a WaitForFirstConsumer claim does), and so does a pod with
+//     host ports or image rows while the option sweep_ports_images is 0;
+//   - vform: both options on and some scenario holds a volume pod.  Every scenario's volume columns
+//     are packed; on the k_simple family every scenario passed vol_form_admit on its own columns and
+//     the kernel is k_simple_vol_sweep, on the largest workgroup whose two slots per lane fit its LDS;
 //   - form: the option is on and some scenario holds such a pod.  Then every scenario gets records
 //     of the ports-and-images form (build_spods force: its 13-bit limit on raw NodeAffinity, zero
 //     masks for pods without ports) and the kernel is k_simple_pi_sweep;
@@ -5477,6 +5557,7 @@ extern "C" {
 // Needs no device.
 struct SweepPlan {
   bool simple = false, form = false;
+  bool vform = false;  // options sweep_ports_images and sweep_volumes on and some scenario holds a volume pod
   int code = GP_OK, scen = -1, pod = -1;  // why k_schedule / why refused, and where
   int total_pods = 0, max_pods = 0, max_nodes = 0, max_keys = 0;
   Geometry g;
@@ -5484,12 +5565,13 @@ struct SweepPlan {
   std::vector<std::vector<SPod>> spods;  // simple: every scenario's records
   std::vector<SPort> sports;             // simple && form: the masks in the order of `chosen`, + RING of padding
   std::vector<int32_t> pod_off;          // ... and every scenario's first
+  std::vector<std::vector<SVol>> svols;  // simple && vform: every scenario's volume records
 };
 
 static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* clusters, const kss_podset* podsets,
                       SweepPlan& pl) {
   pl = SweepPlan{};
-  const bool allow = opt(O_SWEEP_PI) != 0;
+  const bool allow = opt(O_SWEEP_PI) != 0, allow_vol = allow && opt(O_SWEEP_VOL) != 0;
   for (int s = 0; s < n_scen; s++) {
     pl.total_pods += podsets[s].n_pods;
     pl.max_pods = std::max(pl.max_pods, podsets[s].n_pods);
@@ -5498,7 +5580,21 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
     const PlanNeeds q = plan_needs(clusters[s].key_card, clusters[s].key_flags, &podsets[s], podsets[s].n_pods);
     pl.need.bins_cap = std::max(pl.need.bins_cap, q.bins_cap);
     pl.need.general |= q.general;
-    if (q.volumes || (q.ports_images && !allow)) {  // the first refusing pod; a volume pod before the others
+    if (q.volumes && allow_vol) {  // admitted, but for WaitForFirstConsumer claims: the assume cache is not packed
+      for (int i = 0; i < podsets[s].n_pods; i++) {
+        const kss_pod& p = podsets[s].pods[i];
+        for (int e = 0; e < p.vol_len; e++)
+          if (podsets[s].vols[p.vol_off + e].kind == KSS_VOL_BIND_WFFC) {
+            pl.scen = s;
+            pl.pod = i;
+            pl.code = GP_VOL_WFFC;
+            return fail(KSS_E_UNSUPPORTED,
+                        "scenario sweeps: pods with an unbound WaitForFirstConsumer claim take kss_schedule_batch, one "
+                        "scenario at a time, whatever the option sweep_volumes says");
+          }
+      }
+      pl.vform = true;
+    } else if (q.volumes || (q.ports_images && !allow)) {  // the first refusing pod; a volume pod before the others
       for (int i = 0; i < podsets[s].n_pods; i++) {
         const kss_pod& p = podsets[s].pods[i];
         if (q.volumes ? p.vol_len > 0 : pod_ports_images(p)) {
@@ -5515,7 +5611,7 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
         }
       }
     }
-    pl.form |= q.ports_images;  // (no volumes here, and the option is on)
+    pl.form |= q.ports_images || (q.volumes && allow_vol);  // (the option is on; the volumes form is a variant of that form)
   }
   // one workgroup per scenario: at most two node slots per lane (C5, 1,000 nodes: 512
   // threads ran the 512-scenario sweep in 16.5 ms against 23.7 ms at 256)
@@ -5531,7 +5627,19 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
     pl.pod = pod;
     return 0;
   };
-  if (opt(O_NO_SIMPLE) || !simple_fits(pl.g, 0, pl.form)) return demote(GP_SWEEP_GEOMETRY, -1, -1);
+  // The volumes form costs 180 B of LDS per node slot (simple_lds_bytes_vol): two slots per lane of the
+  // preferred workgroup may not fit.  In this form only, the largest workgroup (a multiple of 64 lanes,
+  // at most the preference) whose geometry fits; none: k_schedule, on the preferred geometry.
+  if (pl.vform && !opt(O_NO_SIMPLE) && !simple_fits(pl.g, 0, true, true)) {
+    for (int t = (pref - 1) / 64 * 64; t >= 64; t -= 64) {
+      Geometry g2;
+      if (pick_geometry(pl.max_nodes, 1, t, g2) && g2.threads <= pref && simple_fits(g2, 0, true, true)) {
+        pl.g = g2;
+        break;
+      }
+    }
+  }
+  if (opt(O_NO_SIMPLE) || !simple_fits(pl.g, 0, pl.form, pl.vform)) return demote(GP_SWEEP_GEOMETRY, -1, -1);
   if (pl.need.general) {
     for (int s = 0; s < n_scen; s++)
       for (int i = 0; i < podsets[s].n_pods; i++)
@@ -5542,10 +5650,20 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
   for (int i = 0; i < prof->fit_n; i++)
     if (!(prof->fit_weight[i] >= 0 && prof->fit_weight[i] < (1ll << 20))) return demote(GP_SWEEP_VALUES, -1, -1);
   pl.spods.resize((size_t)n_scen);
+  if (pl.vform) pl.svols.resize((size_t)n_scen);
   if (pl.form) pl.sports.reserve((size_t)pl.total_pods + RING);
   for (int s = 0; s < n_scen; s++) {
     const kss_cluster& cl = clusters[s];
-    if (cl.n_scalar != 0) return demote(GP_SWEEP_SCALAR, s, -1);
+    if (cl.n_scalar != 0) {
+      // The volumes form only: extended resources that no pod of the scenario requests and the profile
+      // does not score decide nothing (NodeResourcesFit checks the scalars a pod requests; attach limits
+      // published as attachable-volumes-* are such columns), so the scenario runs with none.
+      bool idle = pl.vform && scalar_fast_ok(*prof, cl.n_scalar);
+      for (int i = 0; i < podsets[s].n_pods && idle; i++)
+        for (int r = 0; r < cl.n_scalar; r++)
+          idle &= podsets[s].pods[i].fit_request[3 + r] == 0 && podsets[s].pods[i].commit_req[3 + r] == 0;
+      if (!idle) return demote(GP_SWEEP_SCALAR, s, -1);
+    }
     for (size_t i = 0; i < 3 * (size_t)cl.n_nodes; i++)
       if (!(cl.alloc[i] >= 0 && cl.alloc[i] < (1ll << 46))) return demote(GP_SWEEP_VALUES, s, -1);
     F64Bounds bc, bp;
@@ -5553,7 +5671,24 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
     f64_bounds_pods(&podsets[s], bp);
     if (!f64_exact(bc, bp, podsets[s].n_pods)) return demote(GP_SWEEP_VALUES, s, -1);
     PiRecords pi;
-    if (!build_spods(&podsets[s], 0, pl.spods[s], nullptr, pl.form ? &pi : nullptr, false, pl.form)) {
+    // the volumes form: vol_form_admit per scenario, condition 4 on the scenario's own columns
+    const size_t Ns = (size_t)std::max(cl.n_nodes, 0);
+    std::vector<int32_t> att_max((size_t)std::max(cl.n_vol_keys, 1), 0), lim_max((size_t)std::max(cl.n_vol_keys, 1), -1);
+    VolAdmit va;
+    if (pl.vform) {
+      for (int k = 0; k < cl.n_vol_keys; k++)
+        for (size_t n = 0; n < Ns; n++) {
+          att_max[(size_t)k] = std::max(att_max[(size_t)k], cl.vol_attached[(size_t)k * Ns + n]);
+          lim_max[(size_t)k] = std::max(lim_max[(size_t)k], cl.vol_limit[(size_t)k * Ns + n]);
+        }
+      va.n_rows = cl.n_vol_rows;
+      va.n_keys = cl.n_vol_keys;
+      va.row_key = cl.vol_row_key;
+      va.att_max = att_max.data();
+      va.lim_max = lim_max.data();
+    }
+    if (!build_spods(&podsets[s], 0, pl.spods[s], nullptr, pl.form ? &pi : nullptr, false, pl.form, pl.vform ? &va : nullptr)) {
+      if (pl.vform && pi.vol_code != GP_OK) return demote(pi.vol_code, s, pi.vol_pod);  // the form's own reason
       // (no programs, no volumes: fill_spod refused a pod's preferred NodeAffinity weights)
       const int64_t lim = pl.form ? (int64_t)SWPI_NA_MAX : 0xFFFFF;
       for (int i = 0; i < podsets[s].n_pods; i++) {
@@ -5568,6 +5703,7 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
       pl.pod_off.push_back((int32_t)pl.sports.size());
       pl.sports.insert(pl.sports.end(), pi.ports.begin(), pi.ports.begin() + podsets[s].n_pods);
     }
+    if (pl.vform) pl.svols[s].swap(pi.vols);
   }
   // the ring's prefetch distance of padding: the last scenario's prefetch stays inside the allocation
   if (pl.form) pl.sports.resize((size_t)pl.total_pods + RING, SPort{});
@@ -5601,7 +5737,23 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   sw->g = pl.g;
   sw->simple = pl.simple;
   sw->form = pl.form;
-  const bool simple = pl.simple, form = pl.form;
+  sw->vform = pl.vform;
+  const bool simple = pl.simple, form = pl.form, vform = pl.vform;
+  // the volumes form's per-scenario pieces: lim columns and SVol records (inputs), used / att (mutable)
+  std::vector<SVolLaunch> vls(vform && simple ? (size_t)n_scen : 0);
+  auto pack_vol_inputs = [&](Packer& P, int s) {
+    const size_t N = (size_t)std::max(clusters[s].n_nodes, 1);
+    vls[(size_t)s].lim = P.put<uint64_t>(nullptr, 2 * N);
+    if (P.h) vol_pack_host(&clusters[s], nullptr, nullptr, reinterpret_cast<uint64_t*>(P.h + P.last));
+    vls[(size_t)s].svols = P.put(pl.svols[(size_t)s].data(), pl.svols[(size_t)s].size(), pl.svols[(size_t)s].size() + RING);
+  };
+  auto pack_vol_mutable = [&](Packer& P, int s) {
+    const size_t N = (size_t)std::max(clusters[s].n_nodes, 1);
+    vls[(size_t)s].used = P.put<uint64_t>(nullptr, N);
+    if (P.h) vol_pack_host(&clusters[s], reinterpret_cast<uint64_t*>(P.h + P.last), nullptr, nullptr);
+    vls[(size_t)s].att = P.put<uint64_t>(nullptr, 2 * N);
+    if (P.h) vol_pack_host(&clusters[s], nullptr, reinterpret_cast<uint64_t*>(P.h + P.last), nullptr);
+  };
   std::vector<std::vector<SPod>>& spods = pl.spods;
   // layout: [inputs][pristine state][jobs] uploaded; [live state][chosen][meta][err][gran][stat]
   // (the form on the k_simple family: [masks][pod offsets] behind the jobs, uploaded with them)
@@ -5610,12 +5762,14 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   Packer dry;
   for (int s = 0; s < n_scen; s++) {
     in_off[s] = dry.o;
-    pack_inputs(dry, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form);
+    pack_inputs(dry, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form, vform);
+    if (vform && simple) pack_vol_inputs(dry, s);
   }
   sw->pristine_off = dry.o;
   for (int s = 0; s < n_scen; s++) {
     mut_off[s] = dry.o;
-    pack_mutable(dry, &clusters[s], jobs[s], form);
+    pack_mutable(dry, &clusters[s], jobs[s], form, vform);
+    if (vform && simple) pack_vol_mutable(dry, s);
   }
   sw->mut_bytes = dry.o - sw->pristine_off;
   sw->jobs_off = dry.o;
@@ -5625,6 +5779,10 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
     sw->sports_off = dry.last;
     dry.put<int32_t>(nullptr, (size_t)n_scen);
     sw->podoff_off = dry.last;
+  }
+  if (vform && simple) {
+    dry.put<SVolLaunch>(nullptr, (size_t)n_scen);
+    sw->vls_off = dry.last;
   }
   sw->up_bytes = dry.o;
   sw->live_off = dry.o;
@@ -5645,7 +5803,7 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   // k_static time it hides when both share the CUs)
   if (simple) hipSetDevice(device);  // the budget follows this device's free memory
   sw->chunk = simple ? static_chunk(sum_nodes, sw->max_pods) : 0;
-  const bool dbl = simple && sw->chunk < sw->max_pods && opt(O_SWEEP_PIPE) != 0;
+  const bool dbl = simple && !vform && sw->chunk < sw->max_pods && opt(O_SWEEP_PIPE) != 0;  // (the volumes form: one stream)
   if (dbl) sw->chunk = static_chunk(2 * sum_nodes, sw->max_pods);
   const int halves = dbl ? 2 : 1;
   if (simple) {
@@ -5674,10 +5832,22 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   auto work = [&](int t) {
     for (int s = t; s < n_scen; s += nth) {
       Packer P{img.get(), sw->arena, in_off[s]};
-      pack_inputs(P, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form);
+      pack_inputs(P, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form, vform);
+      if (vform && simple) {
+        pack_vol_inputs(P, s);
+        jobs[s].c.n_scalar = 0;  // (sweep_plan: its extended resources are idle; the loop keeps no scalar columns)
+      }
       // host bytes at the pristine position, device pointers at the live position
       Packer M{img.get(), sw->arena + (sw->live_off - sw->pristine_off), mut_off[s]};
-      pack_mutable(M, &clusters[s], jobs[s], form);
+      pack_mutable(M, &clusters[s], jobs[s], form, vform);
+      if (vform && simple) {
+        pack_vol_mutable(M, s);
+        const SVolLaunch K = vol_launch_consts(&clusters[s], *prof);
+        for (int k = 0; k < SV_KEYS; k++) vls[(size_t)s].keyrows[k] = K.keyrows[k];
+        vls[(size_t)s].key_on = K.key_on;
+        vls[(size_t)s].key_csi = K.key_csi;
+        vls[(size_t)s].vr_on = K.vr_on;
+      }
       DevJob& j = jobs[s];
       j.n_pods = podsets[s].n_pods;
       j.commit = 1;
@@ -5709,6 +5879,7 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
     memcpy(img.get() + sw->sports_off, pl.sports.data(), sizeof(SPort) * pl.sports.size());
     memcpy(img.get() + sw->podoff_off, pl.pod_off.data(), sizeof(int32_t) * pl.pod_off.size());
   }
+  if (vform && simple) memcpy(img.get() + sw->vls_off, vls.data(), sizeof(SVolLaunch) * vls.size());
   if (hipMemcpy(sw->arena, img.get(), sw->up_bytes, hipMemcpyHostToDevice) != hipSuccess) {
     fail(KSS_E_DEVICE, "sweep upload failed");
     return nullptr;
@@ -5744,7 +5915,8 @@ int kss_sweep_run(kss_sweep* sw, int32_t* chosen_out, double* device_ms) {
     rc = launch_simple(st, sw->g, sw->n_scen, jobs, sw->prof, sw->max_pods, sw->max_nodes, sw->chunk, nullptr, 0, err, nullptr,
                        nullptr, nullptr, 0, false, nullptr, sw->max_keys, sw->st2, &sw->pev, 0, 0, false,
                        sw->form ? reinterpret_cast<const SPort*>(sw->arena + sw->sports_off) : nullptr,
-                       sw->form ? reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off) : nullptr);
+                       sw->form ? reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off) : nullptr,
+                       sw->vform ? reinterpret_cast<const SVolLaunch*>(sw->arena + sw->vls_off) : nullptr);
   else
     rc = launch_schedule(st, sw->g, sw->n_scen, sw->need.bins_cap + (sw->prof.pct_nodes_to_score < 100 ? 1 : 0),
                          sw->need.general, sw->max_keys, jobs, sw->prof, nullptr, err);
@@ -5781,7 +5953,7 @@ int kss_sweep_info(kss_sweep* sw, double* stage_ms, int32_t* kernel, int64_t* up
 
 int kss_sweep_form(kss_sweep* sw) {
   if (!sw) return fail(KSS_E_INVAL, "null sweep");
-  return sw->form ? 1 : 0;
+  return sw->vform ? 2 : (sw->form ? 1 : 0);  // 2: a volume program somewhere, the volume columns packed as well
 }
 
 void kss_sweep_destroy(kss_sweep* sw) {
@@ -6226,9 +6398,12 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
     if (ps->pods[i].names_len >= 0) names_pod = i;
   const bool win = num_feasible_to_find(cl->n_nodes, prof->pct_nodes_to_score) < cl->n_nodes;
   const bool spread_def = out3[0] == 2 && same_profile(*prof, default_profile_c()) && !opt(O_FOLD);
-  int vol_pod = -1;  // k_simple's volumes form (the plan above admitted the batch to it) has no window variant
-  for (int i = 0; i < ps->n_pods && vol_pod < 0 && out3[0] == 1; i++)
-    if (ps->pods[i].vol_len > 0) vol_pod = i;
+  // k_simple's volumes form (the plan above admitted the batch to it) runs the window only with the
+  // option simple_volumes_window
+  int vol_pod = -1;
+  if (out3[0] == 1 && !opt(O_SIMPLE_VOL_WIN))
+    for (int i = 0; i < ps->n_pods && vol_pod < 0; i++)
+      if (ps->pods[i].vol_len > 0) vol_pod = i;
   if (win && vol_pod >= 0) {
     out3[0] = 0;
     out3[1] = vol_pod;
@@ -6294,7 +6469,7 @@ int kss_plan_sweep(const kss_profile* prof, int32_t n_scen, const kss_cluster* c
   SweepPlan pl;
   const int rc = sweep_plan(prof, n_scen, clusters, podsets, pl);
   out[0] = pl.simple ? 1 : 0;
-  out[1] = pl.form ? 1 : 0;
+  out[1] = pl.vform ? 2 : (pl.form ? 1 : 0);
   out[2] = pl.scen;
   out[3] = pl.pod;
   return rc ? rc : pl.code;
@@ -6425,9 +6600,13 @@ static const void* simple_pi_sweep_fn(bool def) {
 // k_simple's volumes form (option simple_volumes, with simple_ports_images): kss_simple.cuh SVol.
 // Defined here, behind every other kernel, so those keep their places in the code object.
 // ---------------------------------------------------------------------------
-// The loop kernel: k_simple_pi's body (no window instantiation: a windowed batch with a volume
-// program stays on k_schedule) with the launch block `vl` as one more trailing argument.
-template <bool DEF>
+// The loop kernel: k_simple_pi's body with the launch block `vl` as one more trailing argument.
+// WIN: the percentageOfNodesToScore window (option simple_volumes_window; without it a windowed
+// batch with a volume program stays on k_schedule).  The window passes carry the volume verdict where
+// they carry the NodePorts verdict -- before the feasible counts and the cut -- and simple_sync_win
+// commits the volume columns with the row (simple_commit_lanes), so the window form needs nothing of
+// its own: one job on one part, per-wave or whole-workgroup, XCD-local or not.
+template <bool DEF, bool WIN>
 __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_vol(const DevJob* __restrict__ jobs, kss_profile prof, int W,
                                                                 int cap, int k0, int k1, unsigned long long* gran, int* err,
                                                                 unsigned long long* stamps, XPeers X, unsigned epoch0,
@@ -6436,8 +6615,9 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_vol(const DevJob* __
   extern __shared__ __attribute__((aligned(16))) long long smem[];
   SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
   const int Wl = X.n > 1 ? X.wl : W;
+  auto ctr_off = [&] { return xcd_ctr_off<WIN>(W); };
   int xs = 0;  // as k_simple
-  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return 2 * (size_t)W * SX_VALS; }, W, err)) < 0) return;
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, ctr_off, W, err)) < 0) return;
   const int ji = X.xcd_local ? 0 : blockIdx.x / Wl, w = X.xcd_local ? xs : X.w_off + (int)(blockIdx.x % Wl);
   const DevJob job = jobs[ji];
   constexpr kss_profile def_prof = default_profile_c();
@@ -6448,6 +6628,47 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_vol(const DevJob* __
   unsigned long long* sp = ji == 0 ? stamps : nullptr;
   const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
   if (per <= PW_LANES * nwave)
+    simple_schedule<DEF, true, WIN, true, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                                job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                                sports, vl);
+  else
+    simple_schedule<DEF, false, WIN, true, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
+                                                 job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
+                                                 sports, vl);
+}
+
+static const void* simple_vol_fn(bool def, bool win) {
+  return win ? (def ? (const void*)k_simple_vol<true, true> : (const void*)k_simple_vol<false, true>)
+             : (def ? (const void*)k_simple_vol<true, false> : (const void*)k_simple_vol<false, false>);
+}
+
+// The volumes form of a scenario sweep (options sweep_ports_images and sweep_volumes): k_simple_pi_sweep's
+// shape -- many jobs, one workgroup each, both modes within one ragged sweep, no window, no XCD-local
+// grid -- with vls[ji] the launch block of job ji: its constants, its used / att columns in the
+// sweep's mutable arena (restored by every run, carried through HBM between chunk launches), its lim
+// columns and its own SVol array (indexed by the job's pod, like spods).
+template <bool DEF>
+__global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_vol_sweep(const DevJob* __restrict__ jobs, kss_profile prof, int W,
+                                                                      int cap, int k0, int k1, unsigned long long* gran,
+                                                                      int* err, unsigned long long* stamps, XPeers X,
+                                                                      unsigned epoch0, int stat_row0, int k_find,
+                                                                      const SPort* sports_all, const int32_t* pod_off,
+                                                                      const SVolLaunch* vls) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SimpleHdr& H = *reinterpret_cast<SimpleHdr*>(smem);
+  const int Wl = X.n > 1 ? X.wl : W;
+  const int ji = blockIdx.x / Wl, w = X.w_off + (int)(blockIdx.x % Wl);
+  const DevJob job = jobs[ji];
+  constexpr kss_profile def_prof = default_profile_c();
+  if (!DEF) stage_profile(H, jobs[ji].prof);
+  const kss_profile& P = DEF ? def_prof : H.prof;
+  const int per = (job.c.N + W - 1) / W, nwave = (int)(blockDim.x >> 6);
+  unsigned long long* g = gran ? gran + (size_t)ji * 2 * W * SX_VALS : nullptr;
+  unsigned long long* sp = ji == 0 ? stamps : nullptr;
+  const uint32_t* stat = job.stat + (size_t)stat_row0 * (size_t)job.c.N;
+  const SPort* sports = sports_all + pod_off[ji];
+  const SVolLaunch* vl = vls + ji;
+  if (per <= PW_LANES * nwave)
     simple_schedule<DEF, true, false, true, true>(job.c, job.spods, stat, job.P.ints, k0, min(k1, job.n_pods), job.chosen,
                                                   job.meta, P, W, w, cap, g, X, epoch0, err, sp, smem, k_find, job.cursor,
                                                   sports, vl);
@@ -6457,7 +6678,9 @@ __global__ __launch_bounds__(KSS_MAX_THREADS) void k_simple_vol(const DevJob* __
                                                    sports, vl);
 }
 
-static const void* simple_vol_fn(bool def) { return def ? (const void*)k_simple_vol<true> : (const void*)k_simple_vol<false>; }
+static const void* simple_vol_sweep_fn(bool def) {
+  return def ? (const void*)k_simple_vol_sweep<true> : (const void*)k_simple_vol_sweep<false>;
+}
 
 // The static part: the volume filters that no commit changes, over the words k_static_pi just wrote
 // for pods [k0, k1) x rows [n_lo, n_hi) of the one job.  A node whose word passed (verdict 0) and
@@ -6471,7 +6694,8 @@ static const void* simple_vol_fn(bool def) { return def ? (const void*)k_simple_
 constexpr uint32_t SW_VOLUME_STATIC = 5;
 __global__ __launch_bounds__(256) void k_static_vol(const DevJob* __restrict__ jobs, kss_profile prof, int k0, int k1, int n_lo,
                                                     int n_hi, const SVolLaunch* vl) {
-  const DevJob& job = jobs[0];
+  const DevJob& job = jobs[blockIdx.z];  // (a sweep: one launch block and SVol array per job)
+  vl += blockIdx.z;
   const DevCluster& c = job.c;
   const size_t N = (size_t)c.N;
   const int n = n_lo + (int)(blockIdx.x * 256 + threadIdx.x);
@@ -6511,8 +6735,9 @@ __global__ __launch_bounds__(256) void k_static_vol(const DevJob* __restrict__ j
 }
 
 static void launch_static_vol(hipStream_t st, const DevJob* jobs, const kss_profile& pr, int k0, int k1, int n_lo, int n_hi,
-                              const SVolLaunch* vl) {
-  const dim3 grid((unsigned)(std::max(n_hi - n_lo, 1) + 255) / 256, (unsigned)((k1 - k0 + STATIC_PODS - 1) / STATIC_PODS));
+                              const SVolLaunch* vl, int n_jobs) {
+  const dim3 grid((unsigned)(std::max(n_hi - n_lo, 1) + 255) / 256, (unsigned)((k1 - k0 + STATIC_PODS - 1) / STATIC_PODS),
+                  (unsigned)std::max(n_jobs, 1));
   hipLaunchKernelGGL(k_static_vol, grid, dim3(256), 0, st, jobs, pr, k0, k1, n_lo, n_hi, vl);
 }
 

@@ -1450,6 +1450,12 @@ constexpr int SXW_E2 = 4;     // the cut shard's granules per epoch parity: d, T
 constexpr int SXW_CUR = 2;    // split grids: the end-of-launch cursor granule behind the cut granules (+ pad)
 // The window's granules of one launch (8-byte words of the exchange buffer / an inbox half).
 constexpr size_t sxw_words(int W) { return 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 + SXW_CUR; }
+// Where an XCD-local grid's claim counters sit in the exchange buffer of k_simple and its forms
+// (claim_xcd_shard's ctr_off): behind the statistics granules, under the window behind its cut granules.
+template <bool WIN>
+__host__ __device__ constexpr size_t xcd_ctr_off(int W) {
+  return WIN ? 2 * (size_t)W * SXW_VALS + 2 * SXW_E2 : 2 * (size_t)W * SX_VALS;
+}
 
 __device__ __forceinline__ void win_acc(uint32_t (&u)[12], bool c0, bool c1, int part, const SVal& e) {
 #pragma unroll
@@ -2351,7 +2357,7 @@ __device__ __forceinline__ void simple_schedule(DevCluster c, const SPod* __rest
       // halves alternate by chunk), and this address is written again only two chunks later, at
       // the end of a launch whose per-pod exchanges need every part -- so behind this part's poll,
       // which precedes that launch in its stream.  The tag is above every tag the loop used.
-      const size_t co = 2 * (size_t)W * SXW_VALS + 2 * SXW_E2;
+      const size_t co = xcd_ctr_off<true>(W);  // (a split grid is never XCD-local: the same words, behind the cut granules)
       ++epoch;
       if (w == wss && tid == 0) xpub(X, gran, co, ((unsigned long long)epoch << 32) | (uint32_t)wsx);
       if (w == X.w_off && tid == 0) {

@@ -713,7 +713,8 @@ class Context:
 
     def last_simple_form(self) -> Dict[str, int]:
         """{volumes, lds_bytes} of the last run (kss_last_simple_form): volumes 1 when k_simple ran its
-        volumes form (option simple_volumes), lds_bytes the loop kernel's dynamic LDS per workgroup."""
+        volumes form (option simple_volumes; under the window: simple_volumes_window), lds_bytes the
+        loop kernel's dynamic LDS per workgroup."""
         out = (C.c_int32 * 2)()
         check(lib().kss_last_simple_form(self.h, out))
         return {"volumes": out[0], "lds_bytes": out[1]}
@@ -809,7 +810,7 @@ class Sweep:
         if form < 0:
             check(form)
         return {"stage_ms": ms.value, "kernel": "k_simple" if k.value == 1 else "k_schedule", "upload_bytes": b.value,
-                "ports_images": bool(form)}
+                "ports_images": bool(form), "volumes": form == 2}
 
     def close(self):
         if getattr(self, "h", None):
@@ -882,13 +883,15 @@ def plan_service(cluster: abi.Cluster, podset: abi.PodSet, profile: Optional[abi
     return {"chain": int(out[0]), "pod": int(out[1]), "reason": lib().kss_plan_reason(out[2]).decode()}
 
 
-def plan_sweep(profile: abi.Profile, clusters: List[abi.Cluster], podsets: List[abi.PodSet]) -> dict:
+def plan_sweep(profile: abi.Profile, clusters: List[abi.Cluster], podsets: List[abi.PodSet], detail: bool = False) -> dict:
     """Host-only: the routing kss_sweep_create would choose for these scenarios (kss_plan_sweep; the
     same function decides both): the kernel of the whole sweep, whether it runs in the
     ports-and-images form, and the first scenario and pod that keep it off the k_simple family (-1:
-    none, or no single one) with the reason.  Follows the option sweep_ports_images; raises KssError
-    (-95) exactly where Sweep(...) would: a pod with a volume program, or with the option 0 a pod with
-    host ports or node-cached images."""
+    none, or no single one) with the reason.  Follows the options sweep_ports_images and sweep_volumes;
+    raises KssError (-95) exactly where Sweep(...) would: a pod with a volume program (with both options
+    1: only a WaitForFirstConsumer claim), or with sweep_ports_images 0 a pod with host ports or
+    node-cached images.  detail=True adds "volumes": some pod holds a volume program and the sweep packs
+    the volume columns (kernel k_simple: the volumes form, k_simple_vol_sweep)."""
     n = len(clusters)
     carr = (abi.Cluster * max(n, 1))(*clusters)
     parr = (abi.PodSet * max(n, 1))(*podsets)
@@ -896,5 +899,8 @@ def plan_sweep(profile: abi.Profile, clusters: List[abi.Cluster], podsets: List[
     rc = lib().kss_plan_sweep(C.byref(profile), n, carr, parr, out)
     if rc < 0:
         check(rc)
-    return {"kernel": "k_simple" if out[0] == 1 else "k_schedule", "form": bool(out[1]), "scenario": int(out[2]),
+    plan = {"kernel": "k_simple" if out[0] == 1 else "k_schedule", "form": bool(out[1]), "scenario": int(out[2]),
             "pod": int(out[3]), "reason": lib().kss_plan_reason(rc).decode()}
+    if detail:
+        plan["volumes"] = out[1] == 2
+    return plan

@@ -12,9 +12,13 @@ bounds are asserted on the CPU.  Each mode is checked against the C oracle (chos
 vol_count / vol_attached) before anything is timed; then the two modes alternate, `--pairs` times,
 each run a reset and one kss_schedule_batch (wall clock around the call, which ends in the read-back
 of the outcomes, and the library's device time of the launches), at percentageOfNodesToScore = 100
-(the form has no window variant).  Prints one JSON line; --out writes it to a file as well.
+by default.  --pct P (below 100; 0 is the adaptive window, the simulator's own setting) runs the
+windowed search instead: the form's window kernels (option simple_volumes_window = 1) against
+simple_volumes_window = 0, where the batch stays on k_schedule; nextStartNodeIndex is checked against
+the oracle as well.  Prints one JSON line; --out writes it to a file as well.
 
   python tools/volume_bench.py --out profiles/volume_bench.json
+  python tools/volume_bench.py --pct 0 --out profiles/volume_bench_pct0.json
 """
 import argparse
 import json
@@ -103,6 +107,7 @@ def main():
     ap.add_argument("--bound", type=int, default=5000)
     ap.add_argument("--pods", type=int, default=10000)
     ap.add_argument("--pairs", type=int, default=7)
+    ap.add_argument("--pct", type=int, default=100, help="percentageOfNodesToScore (0: adaptive)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     nodes, bound, pods, storage = make(args.seed, args.nodes, args.bound, args.pods)
@@ -114,20 +119,27 @@ def main():
     assert img_pods == n and 0.25 * n < vol_pods < 0.42 * n, (img_pods, vol_pods)
     native.set_option("simple_ports_images", 1)
     native.set_option("simple_volumes", 1)
-    plan = native.plan_podset(cl, ps)
-    assert plan["kernel"] == "k_simple", plan
     want = {0: "k_schedule", 1: "k_simple"}
     prof = abi.default_profile()
+    prof.pct_nodes_to_score = args.pct
+    windowed = args.pct < 100
+    # the option that separates the two modes: under the window the form stays on, its window kernels toggle
+    toggle = "simple_volumes_window" if windowed else "simple_volumes"
+    for on in (0, 1):
+        native.set_option(toggle, on)
+        plan = native.plan_podset(cl, ps, prof)
+        assert plan["kernel"] == want[on], (on, plan)
     ch_o, _, st = oracle_c.schedule(prof, cl, ps, n, N, threads=min(16, os.cpu_count() or 1), record=False,
                                     n_classes=len(cc.classes), n_terms=len(cc.terms))
     out = {"metric": "batch with volume programs: k_simple's volumes form vs k_schedule", "seed": args.seed, "nodes": N,
            "bound": args.bound, "pods": n, "pairs": args.pairs, "volume_rows": cl.n_vol_rows, "limit_keys": cl.n_vol_keys,
-           "pods_with_volume_programs": vol_pods, "pods_with_images": img_pods, "unschedulable": int((ch_o < 0).sum())}
+           "pods_with_volume_programs": vol_pods, "pods_with_images": img_pods, "unschedulable": int((ch_o < 0).sum()),
+           "pct_nodes_to_score": args.pct, "next_start": int(st["next_start"])}
     ctx = native.Context(prof)
     ctx.load(cl)
 
     def run(on):
-        native.set_option("simple_volumes", on)
+        native.set_option(toggle, on)
         ctx.reset()
         t = time.perf_counter()
         chosen = ctx.schedule_batch(ps, n)
@@ -140,6 +152,7 @@ def main():
         assert (chosen == ch_o).all(), "%s differs from the oracle" % want[on]
         vc, va = ctx.volume_state()
         assert (vc == st["vol_count"]).all() and (va == st["vol_attached"]).all(), "volume state differs (%s)" % want[on]
+        assert ctx.next_start_node_index() == st["next_start"], "nextStartNodeIndex differs (%s)" % want[on]
     geom, lds = {}, 0
     wall, dev = {0: [], 1: []}, {0: [], 1: []}
     for _ in range(args.pairs):
@@ -156,7 +169,7 @@ def main():
         return {"median": round(float(np.median(x)), 3), "min": round(float(x.min()), 3), "max": round(float(x.max()), 3)}
 
     ratios = np.array(wall[0]) / np.array(wall[1])
-    out["pct100"] = {
+    out["pct%d" % args.pct] = {
         "geometry": geom, "k_simple_vol_lds_bytes": lds,
         "k_schedule_wall_ms": stats(wall[0]), "k_simple_vol_wall_ms": stats(wall[1]),
         "k_schedule_device_ms": stats(dev[0]), "k_simple_vol_device_ms": stats(dev[1]),
