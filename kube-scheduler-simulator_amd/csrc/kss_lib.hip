@@ -1061,7 +1061,7 @@ struct kss_ctx {
   std::vector<char> stage_host;  // packed host image of a delta upload
   void* pinned = nullptr;     // kss_eval_pod's one-copy result staging (pinned)
   size_t pinned_cap = 0;
-  void* rb = nullptr;         // run_single's read-back staging (pinned): err word, meta, chosen, slot
+  void* rb = nullptr;         // finish_batch's read-back staging (pinned): err word, meta, chosen, slot
   size_t rb_cap = 0;
   void* up = nullptr;         // per-pod calls: pinned image of the pod's pools + the job, one upload
   size_t up_cap = 0;
@@ -1179,7 +1179,7 @@ int upload_podset(hipStream_t st, DevBuf& buf, const kss_podset* ps, DevPods& dp
 }
 
 // One upload for a per-pod call: the pod's pools and `extra` trailing bytes (the launch's
-// job) as one pinned image; run_single fills the job and issues the single copy.
+// job) as one pinned image; launch_batch fills the job and issues the single copy.
 struct PackedUpload {
   char* host = nullptr;  // pinned image
   char* dev = nullptr;
@@ -1396,15 +1396,20 @@ void f64_commit_pod(F64Bounds& c, const kss_pod& p) {
 // A pod of the ports-and-images form (k_simple_pi): host ports or node-cached images.
 bool pod_ports_images(const kss_pod& p) { return (p.port_conflict | p.port_add) != 0 || p.img_len > 0; }
 
+// A pod's preferred-NodeAffinity weight sum (the static word's raw NodeAffinity field bounds it).
+inline int64_t pref_weight_sum(const kss_podset* ps, const kss_pod& p) {
+  int64_t wsum = 0;
+  for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
+  return wsum;
+}
+
 // Compact record of one pod (kss_simple.cuh SPod); false when the preferred NodeAffinity
 // weights do not fit the static word's 20 bits.  pi: a record of the ports-and-images form, which
 // admits NodePorts / ImageLocality pods and whose static word holds 13 bits of NodeAffinity.
 // vol: ... of its volumes form (option simple_volumes; the caller ran vol_form_admit), which admits volume programs.
 bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, bool pi = false, bool vol = false) {
   if ((!pi && pod_ports_images(p)) || (!vol && p.vol_len > 0)) return false;  // NodePorts / ImageLocality / volumes: k_schedule
-  int64_t wsum = 0;
-  for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
-  if (wsum > (pi ? (int64_t)SWPI_NA_MAX : 0xFFFFF)) return false;  // static word: 20 (13) bits of raw NodeAffinity
+  if (pref_weight_sum(ps, p) > (pi ? (int64_t)SWPI_NA_MAX : 0xFFFFF)) return false;  // static word: 20 (13) bits of raw NodeAffinity
   q = SPod{};
   bool all_zero = true;
   for (int r = 0; r < 3 + n_scalar; r++) all_zero &= p.fit_request[r] == 0;
@@ -1452,7 +1457,7 @@ struct PiRecords {
 
 // What the volumes form's admission reads of the cluster.  att_max / lim_max: per key, the largest
 // vol_attached / vol_limit over the nodes (null: condition 4 is checked later, vol_fields_fit --
-// run_single reads the maxima of the device's current columns).
+// plan_batch reads the maxima of the device's current columns).
 struct VolAdmit {
   int n_rows = 0, n_keys = 0;
   const int32_t* row_key = nullptr;
@@ -1460,11 +1465,25 @@ struct VolAdmit {
   const int32_t* lim_max = nullptr;
 };
 
+// A cluster's VolAdmit with condition 4's maxima over its columns as given (att_max / lim_max back the pointers).
+void vol_admit_of(const kss_cluster& cl, std::vector<int32_t>& att_max, std::vector<int32_t>& lim_max, VolAdmit& va) {
+  const size_t N = (size_t)std::max(cl.n_nodes, 0);
+  att_max.assign((size_t)std::max(cl.n_vol_keys, 1), 0);
+  lim_max.assign((size_t)std::max(cl.n_vol_keys, 1), -1);
+  for (int k = 0; k < cl.n_vol_keys; k++)
+    for (size_t n = 0; n < N; n++) {
+      att_max[(size_t)k] = std::max(att_max[(size_t)k], cl.vol_attached[(size_t)k * N + n]);
+      lim_max[(size_t)k] = std::max(lim_max[(size_t)k], cl.vol_limit[(size_t)k * N + n]);
+    }
+  va.n_rows = cl.n_vol_rows, va.n_keys = cl.n_vol_keys, va.row_key = cl.vol_row_key;
+  va.att_max = att_max.data(), va.lim_max = lim_max.data();
+}
+
 int vol_fields_fit(const uint64_t (&add)[SV_KEYS], const int32_t* att_max, const int32_t* lim_max, int n_keys);
 bool vol_form_admit(const kss_podset* ps, const VolAdmit& A, PiRecords& out);
 // svc (staging only): the option service_ports_images asks for that form as well -- the service
 // grid reads the staged records; which kernel a staged batch runs on still follows
-// simple_ports_images alone (run_single).
+// simple_ports_images alone (plan_batch).
 // force (a scenario of a sweep in that form, sweep_plan): records of the form whatever the options
 // and the pods say -- one launch serves every scenario, so a scenario without such a pod gets them
 // too, with zero masks.
@@ -1504,9 +1523,7 @@ bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int
     if (p.n_hard | p.n_soft | p.ipa_len) return false;
     if (!fill_spod(ps, p, n_scalar, out[(size_t)i], form, vol)) {
       if (form && p.vol_len == 0) {  // the form's own limit: weights the 20-bit field would hold
-        int64_t wsum = 0;
-        for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
-        if (wsum <= 0xFFFFF) pi->na_pod = i;
+        if (pref_weight_sum(ps, p) <= 0xFFFFF) pi->na_pod = i;
       }
       return false;
     }
@@ -1633,7 +1650,7 @@ int vol_fields_fit(const uint64_t (&add)[SV_KEYS], const int32_t* att_max, const
 }
 
 // The one admission decision of k_simple's volumes form, shared by kss_plan_podset and stage_spods /
-// run_single: a (validated) batch whose pods' volume programs the form restates exactly.  Fills the
+// plan_batch: a (validated) batch whose pods' volume programs the form restates exactly.  Fills the
 // pods' records and the per-key adds; on refusal the reason code and the first offending pod.
 bool vol_form_admit(const kss_podset* ps, const VolAdmit& A, PiRecords& out) {
   auto refuse = [&](int code, int pod) {
@@ -1754,8 +1771,7 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     std::vector<uint32_t>& R = refs_of[(size_t)i];
     if ((!pi && pod_ports_images(p)) || p.vol_len > 0) return gfail(need, GP_PORTS_IMAGES, i);
     if (!fill_spod(ps, p, n_scalar, g.dyn, pi)) {
-      int64_t wsum = 0;  // the form's own limit, or weights no static word holds
-      for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
+      const int64_t wsum = pref_weight_sum(ps, p);  // the form's own limit, or weights no static word holds
       return gfail(need, pi && wsum <= 0xFFFFF ? GP_SPREAD_PI_NA_WEIGHTS : GP_NA_WEIGHTS, i);
     }
     if (p.n_hard > MAXH || p.n_soft > MAXS) return gfail(need, GP_CONSTRAINTS, i);
@@ -3222,19 +3238,10 @@ static int launch_schedule(hipStream_t st, const Geometry& g, int n_jobs, int bi
   const dim3 grid((unsigned)(n_jobs * g.W)), block((unsigned)g.threads);
   kss_profile pr = prof;
   int W = g.W, npt = g.npt;
-  if (g.W > 1) {
-    void* args[] = {(void*)&jobs, (void*)&pr,   (void*)&W,   (void*)&npt,   (void*)&bins_cap,
-                    (void*)&cache_keys, (void*)&gran, (void*)&err, (void*)&stamps, (void*)&epoch0};
-    if (int rc = launch_resident(fn, grid, block, args, shmem, st)) return rc;
-  } else {
-    if (gen)
-      hipLaunchKernelGGL(k_schedule<true>, grid, block, shmem, st, jobs, pr, W, npt, bins_cap, cache_keys, gran, err, stamps,
-                         epoch0);
-    else
-      hipLaunchKernelGGL(k_schedule<false>, grid, block, shmem, st, jobs, pr, W, npt, bins_cap, cache_keys, gran, err, stamps,
-                         epoch0);
-    HIP_TRY(hipGetLastError());
-  }
+  void* args[] = {(void*)&jobs, (void*)&pr,   (void*)&W,   (void*)&npt,   (void*)&bins_cap,
+                  (void*)&cache_keys, (void*)&gran, (void*)&err, (void*)&stamps, (void*)&epoch0};
+  if (g.W > 1) return launch_resident(fn, grid, block, args, shmem, st);
+  HIP_TRY(hipLaunchKernel(fn, grid, block, args, shmem, st));
   return 0;
 }
 
@@ -3252,12 +3259,18 @@ static bool same_profile(const kss_profile& a, const kss_profile& b) {
 // re-evaluates the candidate after the previous commit).
 static int simple_cap(const Geometry& g) { return g.npt * g.threads; }
 
-static bool simple_fits(const Geometry& g, int nsc, bool pi = false, bool vol = false) {  // pi: k_simple_pi's LDS; vol: k_simple_vol's
+// The loop kernel's dynamic LDS: the table loop's (n_shapes > 0), k_simple_vol's, k_simple_pi's, k_simple's.
+static size_t simple_lds(int cap, int nsc, bool pi, bool vol, int n_shapes = 0) {
+  return n_shapes > 0 ? simple_lds_bytes(cap, 0, n_shapes)
+         : vol        ? simple_lds_bytes_vol(cap, nsc)
+         : pi         ? simple_lds_bytes_pi(cap, nsc)
+                      : simple_lds_bytes(cap, nsc);
+}
+
+static bool simple_fits(const Geometry& g, int nsc, bool pi = false, bool vol = false) {
   const int pf_n = g.threads > 64 ? g.threads - 64 : g.threads;  // prefetch lanes (kss_simple.cuh)
   return g.W <= 64 * SX_CHUNKS && g.npt <= KSS_MAX_NPT && (simple_cap(g) + pf_n - 1) / pf_n <= PF_MAX &&
-         (vol  ? simple_lds_bytes_vol(simple_cap(g), nsc)
-          : pi ? simple_lds_bytes_pi(simple_cap(g), nsc)
-               : simple_lds_bytes(simple_cap(g), nsc)) <= KSS_LDS_BUDGET;
+         simple_lds(simple_cap(g), nsc, pi, vol) <= KSS_LDS_BUDGET;
 }
 
 // k_simple's shape table (k_simple_tab) for a batch of n_shapes resource shapes on geometry g:
@@ -3370,84 +3383,122 @@ static void launch_static(hipStream_t st, bool def, const DevJob* jobs, const ks
   const dim3 sgrid((unsigned)(std::max(n_hi - n_lo, 1) + 1023) / 1024, (unsigned)((k1 - k0 + ppb - 1) / ppb),
                    (unsigned)n_jobs);
   const size_t sh = sizeof(int32_t) * 1024 * (size_t)lk;
-  if (pi && def)  // the ports-and-images form of the word (k_simple_pi reads it)
-    hipLaunchKernelGGL(k_static_pi<true>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
-  else if (pi)
-    hipLaunchKernelGGL(k_static_pi<false>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
-  else if (def)
-    hipLaunchKernelGGL(k_static<true>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
-  else
-    hipLaunchKernelGGL(k_static<false>, sgrid, dim3(256), sh, st, jobs, pr, k0, k1, n_lo, n_hi, lk, row0, ppb);
+  // pi: the ports-and-images form of the word (k_simple_pi reads it)
+  const void* fn = pi ? (def ? (const void*)k_static_pi<true> : (const void*)k_static_pi<false>)
+                      : (def ? (const void*)k_static<true> : (const void*)k_static<false>);
+  void* args[] = {(void*)&jobs, (void*)&pr, (void*)&k0, (void*)&k1, (void*)&n_lo, (void*)&n_hi, (void*)&lk, (void*)&row0, (void*)&ppb};
+  (void)hipLaunchKernel(fn, sgrid, dim3(256), args, sh, st);  // (the callers read hipGetLastError)
 }
 
-// xcd: one job on an XCD-local grid (xcd_slot); a chunk whose launch reports the placement
-// failure (err = 3, no state touched) is synchronised on and run again unrestricted.
-static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const DevJob* jobs, const kss_profile& prof,
-                         int n_pods_max, int max_nodes, int chunk, unsigned long long* gran, size_t gran_bytes, int* err,
-                         unsigned long long* stamps = nullptr, hipEvent_t* ev = nullptr, const SplitRun* split = nullptr,
-                         int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr, int max_keys = 0,
-                         hipStream_t st2 = nullptr, std::vector<hipEvent_t>* pev = nullptr, int k_find = 0,
-                         int n_shapes = 0, bool flat = false, const SPort* sports = nullptr,
-                         const int32_t* pod_off = nullptr, const SVolLaunch* vl = nullptr) {
-  // the volumes form (one job; vl: the launch block on the device, vol_pack_state): k_static_pi +
-  // k_static_vol + k_simple_vol per chunk, then the packed attached counts back into vol_attached
-  // and the pods' own rows into vol_count (k_vol_unpack, k_vol_counts).  No table, no split; the
-  // window (k_find > 0) as the ports-and-images form runs it (the caller checked simple_volumes_window).
-  // ... of a sweep (many jobs; pod_off as in the ports-and-images sweep, vl: SVolLaunch[n_jobs], each with
-  // its scenario's columns and records): k_static_pi + k_static_vol over every job + k_simple_vol_sweep;
-  // the columns are the sweep's own mutable state, so nothing is written back.
-  const bool vol = vl != nullptr, vol_sweep = vol && pod_off != nullptr;
-  if (vol && !vol_sweep && (!sports || n_shapes > 0 || split || n_jobs != 1 || st2))
-    return fail(KSS_E_INVAL, "volumes form: one job of the ports-and-images form, no table or split");
-  if (vol_sweep && (!sports || st2)) return fail(KSS_E_INVAL, "sweep volumes form: the ports-and-images sweep, one stream");
-  // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
-  // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
-  const bool pi = sports != nullptr;
-  // ... of a sweep (many jobs; pod_off: every job's first mask in sports): k_static_pi +
-  // k_simple_pi_sweep.  No table, no window, no split and no XCD-local grid: sweeps pass none of those.
-  const bool pi_sweep = pi && pod_off != nullptr;
-  if (pi_sweep && (n_shapes > 0 || k_find > 0 || split || xcd || nsc != 0))
-    return fail(KSS_E_INVAL, "sweep ports-and-images form: no table, window, split or XCD-local grid");
+// What both loop-kernel launchers take; the defaults are one part, no window, no XCD-local grid.
+struct LoopLaunch {
+  Geometry g;
+  const DevJob* jobs = nullptr;
+  const kss_profile* prof = nullptr;
+  int n_pods = 0, max_nodes = 0, chunk = 1;  // pods [0, n_pods) (many jobs: of the largest), `chunk` per launch
+  int n_keys = 0, nsc = 0, k_find = 0;  // label keys (many jobs: the largest count), extended resources, the window (> 0)
+  unsigned long long *gran = nullptr, *stamps = nullptr;
+  size_t gran_bytes = 0;
+  hipEvent_t* ev = nullptr;         // 2 events per chunk recorded around each loop-kernel launch
+  const SplitRun* split = nullptr;  // a split grid's part
+  bool xcd = false;                 // one job on an XCD-local grid (launch_chunk)
+  int *err = nullptr, *xcd_fallbacks = nullptr;
+};
+
+// One chunk launch.  xcd: on an XCD-local grid (xcd_slot); a launch that reports the placement failure (err = 3:
+// nothing ran, no state touched) is synchronised on and run again unrestricted, as is every later chunk.  args holds &X.
+static int launch_chunk(hipStream_t st, const LoopLaunch& L, const void* fn, dim3 grid, size_t shmem, void** args,
+                        XPeers& X, bool& xcd) {
+  const dim3 block((unsigned)L.g.threads);
+  if (!xcd) {
+    if (L.g.W > 1) return launch_resident(fn, grid, block, args, shmem, st);
+    HIP_TRY(hipLaunchKernel(fn, grid, block, args, shmem, st));
+    return 0;
+  }
+  X.xcd_local = opt(O_XCD_FORCE_FALLBACK) ? 2 : 1;  // 2: placement reported failed (tests)
+  if (int rc = launch_resident(fn, dim3((unsigned)(XCD_GRID_MULT * L.g.W)), block, args, shmem, st)) return rc;
+  int e = 0;
+  HIP_TRY(hipMemcpyAsync(&e, L.err, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  X.xcd_local = 0;
+  if (e != 3) return 0;
+  if (L.xcd_fallbacks) ++*L.xcd_fallbacks;
+  xcd = false;
+  HIP_TRY(dev_zero(L.err, 4, st));
+  HIP_TRY(dev_zero(L.gran, L.gran_bytes, st));
+  return launch_resident(fn, grid, block, args, shmem, st);
+}
+
+// k_simple's family (the sweeps' and the volumes form's kernels are defined at the end of this file).
+static const void* simple_fn(bool def, bool win, bool pi, bool vol, bool sweep, bool tab, bool flat) {
+  if (vol && sweep) return simple_vol_sweep_fn(def);
+  if (pi && sweep) return simple_pi_sweep_fn(def);
+  if (vol) return simple_vol_fn(def, win);
+  if (flat) return pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat;
+  if (tab) return pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab;
+  if (pi)
+    return win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
+               : (def ? (const void*)k_simple_pi<true, false> : (const void*)k_simple_pi<false, false>);
+  return win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
+             : (def ? (const void*)k_simple<true, false> : (const void*)k_simple<false, false>);
+}
+
+// launch_simple's arguments; the defaults are one plain job, one stream.  k_find > 0: one job; on a split
+// grid every part ends the launch with the same nextStartNodeIndex in its own cursor word (simple_schedule).
+struct SimpleLaunch : LoopLaunch {
+  int n_jobs = 1, n_shapes = 0;  // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
   // st2 (with pev, two events per chunk): the static words of chunk i+1 are computed on st2 into the
   // other half of a double-buffered table while k_simple runs chunk i on st (each job's table holds
   // 2 x chunk rows); k_simple of chunk i waits for its k_static, k_static of chunk i+1 for
   // k_simple of chunk i-1 (the last reader of that half)
+  hipStream_t st2 = nullptr;
+  std::vector<hipEvent_t>* pev = nullptr;
+  bool flat = false;   // the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
+  // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
+  // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
+  const SPort* sports = nullptr;
+  // ... of a sweep (many jobs; pod_off: every job's first mask in sports): k_static_pi +
+  // k_simple_pi_sweep.  No table, no window, no split and no XCD-local grid: sweeps pass none of those.
+  const int32_t* pod_off = nullptr;
+  // the volumes form (one job; vl: the launch block on the device, vol_pack_state): k_static_pi + k_static_vol +
+  // k_simple_vol per chunk, then the packed attached counts back into vol_attached and the pods' own rows into
+  // vol_count (k_vol_unpack, k_vol_counts).  No table, no split; the window as the ports-and-images form runs it.
+  // ... of a sweep (pod_off as above, vl: SVolLaunch[n_jobs], each with its scenario's columns and records):
+  // + k_simple_vol_sweep; the columns are the sweep's own mutable state, so nothing is written back.
+  const SVolLaunch* vl = nullptr;
+};
+
+static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
+  const Geometry& g = L.g;
+  const int n_jobs = L.n_jobs, n_pods_max = L.n_pods, chunk = L.chunk;
+  const bool vol = L.vl != nullptr, vol_sweep = vol && L.pod_off != nullptr;
+  if (vol && !vol_sweep && (!L.sports || L.n_shapes > 0 || L.split || n_jobs != 1 || L.st2))
+    return fail(KSS_E_INVAL, "volumes form: one job of the ports-and-images form, no table or split");
+  if (vol_sweep && (!L.sports || L.st2)) return fail(KSS_E_INVAL, "sweep volumes form: the ports-and-images sweep, one stream");
+  const bool pi = L.sports != nullptr, pi_sweep = pi && L.pod_off != nullptr;
+  if (pi_sweep && (L.n_shapes > 0 || L.k_find > 0 || L.split || L.xcd || L.nsc != 0))
+    return fail(KSS_E_INVAL, "sweep ports-and-images form: no table, window, split or XCD-local grid");
   int cap = simple_cap(g);
-  const bool def = same_profile(prof, default_profile_c());
-  // k_find > 0: the percentageOfNodesToScore window (one job; on a split grid every part ends the
-  // launch with the same nextStartNodeIndex in its own cursor word, simple_schedule)
-  const bool win = k_find > 0;
-  // n_shapes > 0: the shape-table kernel (the caller checked shape_table_ok)
-  const bool tab = n_shapes > 0 && def && !win && nsc == 0;
-  const size_t shmem = tab   ? simple_lds_bytes(cap, 0, n_shapes)
-                       : vol ? simple_lds_bytes_vol(cap, nsc)
-                       : pi  ? simple_lds_bytes_pi(cap, nsc)
-                             : simple_lds_bytes(cap, nsc);
-  // flat: the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
-  flat = flat && tab && n_jobs == 1 && !(split && split->X.n > 1);
+  const bool def = same_profile(*L.prof, default_profile_c());
+  const bool win = L.k_find > 0;
+  const bool tab = L.n_shapes > 0 && def && !win && L.nsc == 0;
+  const size_t shmem = simple_lds(cap, L.nsc, pi, vol, tab ? L.n_shapes : 0);
+  const bool flat = L.flat && tab && n_jobs == 1 && !(L.split && L.split->X.n > 1);
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
-  if (flat && gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
+  if (flat && L.gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
     return fail(KSS_E_INVAL, "flat exchange: granule buffer too small");
-  const void* fn = vol_sweep ? simple_vol_sweep_fn(def)
-                   : pi_sweep ? simple_pi_sweep_fn(def)
-                   : vol   ? simple_vol_fn(def, win)
-                   : flat  ? (pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat)
-                   : tab ? (pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab)
-                   : pi  ? (win ? (def ? (const void*)k_simple_pi<true, true> : (const void*)k_simple_pi<false, true>)
-                                : (def ? (const void*)k_simple_pi<true, false> : (const void*)k_simple_pi<false, false>))
-                   : win ? (def ? (const void*)k_simple<true, true> : (const void*)k_simple<false, true>)
-                         : (def ? (const void*)k_simple<true, false> : (const void*)k_simple<false, false>);
-  int last_arg = tab ? n_shapes : k_find;  // k_simple_tab: n_shapes in k_find's place
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  XPeers X = split ? split->X : XPeers{};
+  int last_arg = tab ? L.n_shapes : L.k_find;  // k_simple_tab: n_shapes in k_find's place
+  XPeers X = L.split ? L.split->X : XPeers{};
   const bool sp_grid = X.n > 1;
-  xcd = xcd && !sp_grid && n_jobs == 1 && gran;
-  const dim3 grid((unsigned)(n_jobs * (sp_grid ? X.wl : g.W))), block((unsigned)g.threads);
-  const dim3 xgrid((unsigned)(XCD_GRID_MULT * g.W));
-  kss_profile pr = prof;
+  bool xcd = L.xcd && !sp_grid && n_jobs == 1 && L.gran;
+  const void* fn = simple_fn(def, win, pi, vol, L.pod_off != nullptr, tab, flat);
+  const dim3 grid((unsigned)(n_jobs * (sp_grid ? X.wl : g.W)));
+  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  kss_profile pr = *L.prof;
   int W = g.W, n_lo = 0, n_hi = 0;
-  static_rows(g, X, max_nodes, n_lo, n_hi);
-  const bool pipe = st2 && pev && !sp_grid && !xcd;
+  static_rows(g, X, L.max_nodes, n_lo, n_hi);
+  std::vector<hipEvent_t>* const pev = L.pev;
+  const bool pipe = L.st2 && pev && !sp_grid && !xcd;
   const int n_chunks = (n_pods_max + chunk - 1) / std::max(chunk, 1);
   if (pipe) {
     while ((int)pev->size() < 2 * n_chunks) {
@@ -3457,74 +3508,55 @@ static int launch_simple(hipStream_t st, const Geometry& g, int n_jobs, const De
     }
     // (*pev)[2i]: k_static of chunk i done (st2), (*pev)[2i+1]: k_simple of chunk i done (st)
     HIP_TRY(hipEventRecord((*pev)[1], st));  // st's work so far (the reset) before st2 writes the table
-    HIP_TRY(hipStreamWaitEvent(st2, (*pev)[1], 0));
-    launch_static(st2, def, jobs, pr, n_jobs, 0, std::min(n_pods_max, chunk), n_lo, n_hi, max_keys, 0, pi);
+    HIP_TRY(hipStreamWaitEvent(L.st2, (*pev)[1], 0));
+    launch_static(L.st2, def, L.jobs, pr, n_jobs, 0, std::min(n_pods_max, chunk), n_lo, n_hi, L.n_keys, 0, pi);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord((*pev)[0], st2));
+    HIP_TRY(hipEventRecord((*pev)[0], L.st2));
   }
   for (int k0 = 0; k0 < n_pods_max; k0 += chunk) {
     int k1 = std::min(n_pods_max, k0 + chunk);
-    const int ci_ = k0 / std::max(chunk, 1);
-    int row0 = pipe ? (ci_ & 1) * chunk : 0;
+    const int ci = k0 / std::max(chunk, 1);
+    int row0 = pipe ? (ci & 1) * chunk : 0;
     if (pipe) {
-      HIP_TRY(hipStreamWaitEvent(st, (*pev)[2 * ci_], 0));  // this chunk's static words
+      HIP_TRY(hipStreamWaitEvent(st, (*pev)[2 * ci], 0));  // this chunk's static words
       if (k1 < n_pods_max) {  // the next chunk's, into the other half, once chunk ci-1 no longer reads it
-        if (ci_ > 0) HIP_TRY(hipStreamWaitEvent(st2, (*pev)[2 * (ci_ - 1) + 1], 0));
-        launch_static(st2, def, jobs, pr, n_jobs, k1, std::min(n_pods_max, k1 + chunk), n_lo, n_hi, max_keys,
-                      ((ci_ + 1) & 1) * chunk, pi);
+        if (ci > 0) HIP_TRY(hipStreamWaitEvent(L.st2, (*pev)[2 * (ci - 1) + 1], 0));
+        launch_static(L.st2, def, L.jobs, pr, n_jobs, k1, std::min(n_pods_max, k1 + chunk), n_lo, n_hi, L.n_keys,
+                      ((ci + 1) & 1) * chunk, pi);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord((*pev)[2 * (ci_ + 1)], st2));
+        HIP_TRY(hipEventRecord((*pev)[2 * (ci + 1)], L.st2));
       }
     } else {
-      launch_static(st, def, jobs, pr, n_jobs, k0, k1, n_lo, n_hi, max_keys, 0, pi);
+      launch_static(st, def, L.jobs, pr, n_jobs, k0, k1, n_lo, n_hi, L.n_keys, 0, pi);
       HIP_TRY(hipGetLastError());
       if (vol) {  // VolumeBinding / VolumeZone verdicts into the words just written
-        launch_static_vol(st, jobs, pr, k0, k1, n_lo, n_hi, vl, n_jobs);
+        launch_static_vol(st, L.jobs, pr, k0, k1, n_lo, n_hi, L.vl, n_jobs);
         HIP_TRY(hipGetLastError());
       }
     }
     unsigned epoch0 = 0;
-    unsigned long long* gc = gran;
+    unsigned long long* gc = L.gran;
     if (sp_grid) {
-      epoch0 = split->epoch0 + (unsigned)(k0 / std::max(chunk, 1)) * chunk_span(chunk);
-      split_chunk_view(*split, k0 / std::max(chunk, 1), gran, gc, X);
-    } else if (gran && k0 > 0) {
-      HIP_TRY(dev_zero(gran, gran_bytes, st));
+      epoch0 = L.split->epoch0 + (unsigned)ci * chunk_span(chunk);
+      split_chunk_view(*L.split, ci, L.gran, gc, X);
+    } else if (L.gran && k0 > 0) {
+      HIP_TRY(dev_zero(L.gran, L.gran_bytes, st));
     }
-    unsigned long long* sp = k0 == 0 ? stamps : nullptr;
-    void* args[] = {(void*)&jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
-                    (void*)&gc,   (void*)&err, (void*)&sp, (void*)&X,   (void*)&epoch0, (void*)&row0, (void*)&last_arg,
-                    (void*)&sports, vol && !vol_sweep ? (void*)&vl : (void*)&pod_off,
-                    (void*)&vl};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's / k_simple_vol's two, k_simple_vol_sweep's three; the other kernels take 13)
-    const int ci = k0 / chunk;
-    if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
-    if (xcd) {
-      X.xcd_local = opt(O_XCD_FORCE_FALLBACK) ? 2 : 1;  // 2: placement reported failed (tests)
-      if (int rc = launch_resident(fn, xgrid, block, args, shmem, st)) return rc;
-      int e = 0;
-      HIP_TRY(hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      X.xcd_local = 0;
-      if (e == 3) {  // XCD 0 did not get W workgroups: nothing ran; again, unrestricted
-        if (xcd_fallbacks) ++*xcd_fallbacks;
-        xcd = false;
-        HIP_TRY(dev_zero(err, 4, st));
-        HIP_TRY(dev_zero(gran, gran_bytes, st));
-        if (int rc = launch_resident(fn, grid, block, args, shmem, st)) return rc;
-      }
-    } else if (g.W > 1) {
-      if (int rc = launch_resident(fn, grid, block, args, shmem, st)) return rc;
-    } else {
-      HIP_TRY(hipLaunchKernel(fn, grid, block, args, shmem, st));
-    }
-    if (ev) HIP_TRY(hipEventRecord(ev[2 * ci + 1], st));
+    unsigned long long* sp = k0 == 0 ? L.stamps : nullptr;
+    void* args[] = {(void*)&L.jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
+                    (void*)&gc,     (void*)&L.err, (void*)&sp, (void*)&X, (void*)&epoch0, (void*)&row0, (void*)&last_arg,
+                    (void*)&L.sports, vol && !vol_sweep ? (void*)&L.vl : (void*)&L.pod_off,
+                    (void*)&L.vl};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's / k_simple_vol's two, k_simple_vol_sweep's three; the other kernels take 13)
+    if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci], st));
+    if (int rc = launch_chunk(st, L, fn, grid, shmem, args, X, xcd)) return rc;
+    if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci + 1], st));
     if (pipe) HIP_TRY(hipEventRecord((*pev)[2 * ci + 1], st));
   }
-  hipLaunchKernelGGL(k_counts, dim3((unsigned)((n_pods_max + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, jobs, 0,
+  hipLaunchKernelGGL(k_counts, dim3((unsigned)((n_pods_max + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, L.jobs, 0,
                      n_pods_max);
   HIP_TRY(hipGetLastError());
   if (vol && !vol_sweep) {
-    launch_vol_writeback(st, jobs, max_nodes, n_pods_max, vl);
+    launch_vol_writeback(st, L.jobs, L.max_nodes, n_pods_max, L.vl);
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -3563,16 +3595,35 @@ struct HandoffLayout {
   }
 };
 
+// k_spread's family; the window (default profile, no fold) and the ports-and-images form (no fold; defined at
+// the end of this file) have their own instantiations.  launch_spread refuses the combinations that have none.
+static const void* spread_fn(bool def, bool fold, bool lb, bool win, bool pi) {
+  const void* fn = lb ? (def ? (fold ? (const void*)k_spread<true, true, 256, false> : (const void*)k_spread<true, false, 256, false>)
+                             : (fold ? (const void*)k_spread<false, true, 256, false> : (const void*)k_spread<false, false, 256, false>))
+                      : (def ? (fold ? (const void*)k_spread<true, true, KSS_MAX_THREADS, false>
+                                     : (const void*)k_spread<true, false, KSS_MAX_THREADS, false>)
+                             : (fold ? (const void*)k_spread<false, true, KSS_MAX_THREADS, false>
+                                     : (const void*)k_spread<false, false, KSS_MAX_THREADS, false>));
+  if (win) fn = lb ? (const void*)k_spread<true, false, 256, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, true>;
+  if (pi) fn = spread_pi_fn(def, lb, win);
+  return fn;
+}
+
+// launch_spread's arguments (one job); the default is no checked hand-off.
+struct SpreadLaunch : LoopLaunch {
+  const GpodNeeds* q = nullptr;  // the batch's needs (with the window's count area when k_find > 0)
+  int n_res = 0;                 // its resident count rows
+  unsigned long long *ck = nullptr, *ck_seq = nullptr;  // the checked hand-off's buffer (HandoffLayout), its tag counter
+};
+
 // k_static + k_spread over pods [0, n_pods) of one job, `chunk` pods at a time (node state
-// and counts back in HBM between launches).  ev (optional): 2 events per chunk.
-static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, int n_keys, int n_res,
-                         const DevJob* jobs, const kss_profile& prof, int n_pods, int max_nodes, int chunk,
-                         unsigned long long* gran, size_t gran_bytes, int* err, unsigned long long* stamps = nullptr,
-                         hipEvent_t* ev = nullptr, const SplitRun* split = nullptr, unsigned long long* ck = nullptr,
-                         unsigned long long* ck_seq = nullptr, int nsc = 0, bool xcd = false, int* xcd_fallbacks = nullptr,
-                         int k_find = 0) {
-  int cap = spread_cap(g, (size_t)max_nodes), bins_cap = q.bins_cap, nr = n_res, gq = q.gq, gs = q.gs();
-  size_t shmem = spread_lds(g, q, n_keys, n_res, (size_t)max_nodes, nsc);
+// and counts back in HBM between launches).
+static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
+  const Geometry& g = L.g;
+  const GpodNeeds& q = *L.q;
+  unsigned long long* stamps = L.stamps;
+  int cap = spread_cap(g, (size_t)L.max_nodes), bins_cap = q.bins_cap, nr = L.n_res, gq = q.gq, gs = q.gs();
+  size_t shmem = spread_lds(g, q, L.n_keys, L.n_res, (size_t)L.max_nodes, L.nsc);
   // diagnostic stamps in LDS: as many pods (<= G_NSTAMP, >= 8) as fit beside the shard state
   int nst = 0;
   if (stamps && shmem < KSS_LDS_BUDGET) nst = (int)std::min<size_t>(G_NSTAMP, (KSS_LDS_BUDGET - shmem) / (16 * 8));
@@ -3582,117 +3633,79 @@ static int launch_spread(hipStream_t st, const Geometry& g, const GpodNeeds& q, 
   if (const char* e = getenv("KSS_SPREAD_MIN_LDS"))  // diagnosis: at most one shard per CU
     shmem = std::max(shmem, std::min((size_t)KSS_LDS_BUDGET, (size_t)std::max(0, atoi(e))));
 #endif
-  const bool def = same_profile(prof, default_profile_c());
+  const bool def = same_profile(*L.prof, default_profile_c());
   const bool fold = opt(O_FOLD) != 0;
   const bool lb = g.threads <= 256 && opt(O_SPREAD_LB256);
-  const void* fn = lb ? (def ? (fold ? (const void*)k_spread<true, true, 256, false> : (const void*)k_spread<true, false, 256, false>)
-                             : (fold ? (const void*)k_spread<false, true, 256, false> : (const void*)k_spread<false, false, 256, false>))
-                      : (def ? (fold ? (const void*)k_spread<true, true, KSS_MAX_THREADS, false>
-                                     : (const void*)k_spread<true, false, KSS_MAX_THREADS, false>)
-                             : (fold ? (const void*)k_spread<false, true, KSS_MAX_THREADS, false>
-                                     : (const void*)k_spread<false, false, KSS_MAX_THREADS, false>));
-  // the window (default profile, no fold): its own instantiations
-  if (k_find > 0) {
-    if (!def || fold) return fail(KSS_E_INVAL, "k_spread window: default profile, no statistics fold");
-    fn = lb ? (const void*)k_spread<true, false, 256, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, true>;
-  }
-  // the ports-and-images form (build_gpods need.pi; run_single checked: one part, no fold): its own
-  // instantiations, and k_static_pi's words
-  if (q.pi) {
-    if (fold || split) return fail(KSS_E_INVAL, "k_spread ports-and-images form: one part, no statistics fold");
-    fn = spread_pi_fn(def, lb, k_find > 0);
-  }
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  XPeers X = split ? split->X : XPeers{};
+  if (L.k_find > 0 && (!def || fold)) return fail(KSS_E_INVAL, "k_spread window: default profile, no statistics fold");
+  // the ports-and-images form (build_gpods need.pi; plan_batch checked: one part, no fold): k_static_pi's words
+  if (q.pi && (fold || L.split)) return fail(KSS_E_INVAL, "k_spread ports-and-images form: one part, no statistics fold");
+  XPeers X = L.split ? L.split->X : XPeers{};
   const bool sp_grid = X.n > 1;
-  xcd = xcd && !sp_grid && gran && g.W > 1;
-  const dim3 grid((unsigned)(sp_grid ? X.wl : g.W)), block((unsigned)g.threads);
-  const dim3 xgrid((unsigned)(XCD_GRID_MULT * g.W));
+  bool xcd = L.xcd && !sp_grid && L.gran && g.W > 1;
+  const void* fn = spread_fn(def, fold, lb, L.k_find > 0, q.pi);
+  const dim3 grid((unsigned)(sp_grid ? X.wl : g.W));
+  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   // many shards on one part: the two-level selectHost exchange, its area at the end of the
-  // granule buffer (run_single reserves tl_words)
+  // granule buffer (launch_batch reserves tl_words)
   const size_t tlw = tl_words(g.W);
-  if (!sp_grid && !xcd && gran && g.W > 64 && opt(O_SPREAD_TWO_LEVEL) &&
-      gran_bytes / 8 >= tlw + 2 * (size_t)g.W * (size_t)gs + 16)
-    X.tl = gran + gran_bytes / 8 - tlw, X.tl_red = opt(O_SPREAD_TWO_LEVEL) >= 2;
-  kss_profile pr = prof;
+  if (!sp_grid && !xcd && L.gran && g.W > 64 && opt(O_SPREAD_TWO_LEVEL) &&
+      L.gran_bytes / 8 >= tlw + 2 * (size_t)g.W * (size_t)gs + 16)
+    X.tl = L.gran + L.gran_bytes / 8 - tlw, X.tl_red = opt(O_SPREAD_TWO_LEVEL) >= 2;
+  kss_profile pr = *L.prof;
   int W = g.W, n_lo = 0, n_hi = 0;
-  static_rows(g, X, max_nodes, n_lo, n_hi);
-  for (int k0 = 0; k0 < n_pods; k0 += chunk) {
-    int k1 = std::min(n_pods, k0 + chunk);
-    launch_static(st, def, jobs, pr, 1, k0, k1, n_lo, n_hi, n_keys, 0, q.pi);
+  static_rows(g, X, L.max_nodes, n_lo, n_hi);
+  // the checked node-state hand-off (HandoffCheck): tags increase over the context's life
+  const HandoffLayout hl(g.W, L.n_res, L.max_nodes, L.nsc, q.pi);
+  auto handoff = [&](unsigned long long expect, unsigned long long write) {
+    HandoffCheck hc{};
+    if (!L.ck || !L.ck_seq) return hc;
+    hc.sum = L.ck, hc.expect = expect, hc.write = write;
+    hc.retries = L.err + 1;
+    hc.xcc = (int*)(L.ck + hl.o_xcc);
+    hc.diag = (long long*)(L.ck + hl.o_diag);
+    hc.shadow = (long long*)(L.ck + hl.o_shadow);
+    return hc;
+  };
+  for (int k0 = 0; k0 < L.n_pods; k0 += L.chunk) {
+    int k1 = std::min(L.n_pods, k0 + L.chunk);
+    const int ci = k0 / std::max(L.chunk, 1);
+    launch_static(st, def, L.jobs, pr, 1, k0, k1, n_lo, n_hi, L.n_keys, 0, q.pi);
     HIP_TRY(hipGetLastError());
     // every chunk's tags above the previous chunk's (a line an earlier chunk left in an XCD's
     // L2 never carries a current tag), the buffer zeroed as well
-    unsigned epoch0 = (unsigned)(k0 / std::max(chunk, 1)) * chunk_span(chunk);
-    unsigned long long* gc = gran;
+    unsigned epoch0 = (unsigned)ci * chunk_span(L.chunk);
+    unsigned long long* gc = L.gran;
     if (sp_grid) {
-      epoch0 += split->epoch0;
-      split_chunk_view(*split, k0 / std::max(chunk, 1), gran, gc, X);
-    } else if (gran && k0 > 0) {
-      HIP_TRY(dev_zero(gran, gran_bytes, st));
+      epoch0 += L.split->epoch0;
+      split_chunk_view(*L.split, ci, L.gran, gc, X);
+    } else if (L.gran && k0 > 0) {
+      HIP_TRY(dev_zero(L.gran, L.gran_bytes, st));
     }
     unsigned long long* sp = k0 == 0 ? stamps : nullptr;
-    // the checked node-state hand-off between this call's chunks (HandoffCheck): tags increase
-    // over the context's life, the first chunk of a call checks nothing
-    HandoffCheck hc{};
-    if (ck && ck_seq) {
-      const HandoffLayout hl(g.W, n_res, max_nodes, nsc, q.pi);
-      hc.sum = ck;
-      hc.expect = k0 > 0 ? *ck_seq : 0ull;
-      hc.write = ++*ck_seq;
-      hc.retries = err + 1;
-      hc.xcc = (int*)(ck + hl.o_xcc);
-      hc.diag = (long long*)(ck + hl.o_diag);
-      hc.shadow = (long long*)(ck + hl.o_shadow);
-    }
-    void* args[] = {(void*)&jobs, (void*)&W,  (void*)&cap, (void*)&bins_cap, (void*)&nr,  (void*)&gq, (void*)&gs, (void*)&k0,
-                    (void*)&k1,   (void*)&gc, (void*)&err, (void*)&sp,       (void*)&nst, (void*)&X,  (void*)&epoch0,
-                    (void*)&hc,   (void*)&k_find};
-    const int ci = k0 / chunk;
-    if (ev) HIP_TRY(hipEventRecord(ev[2 * ci], st));
-    if (xcd) {  // as launch_simple: an XCD-local grid, run again unrestricted when placement failed
-      X.xcd_local = opt(O_XCD_FORCE_FALLBACK) ? 2 : 1;  // 2: placement reported failed (tests)
-      if (int rc = launch_resident(fn, xgrid, block, args, shmem, st)) return rc;
-      int e = 0;
-      HIP_TRY(hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      X.xcd_local = 0;
-      if (e == 3) {
-        if (xcd_fallbacks) ++*xcd_fallbacks;
-        xcd = false;
-        HIP_TRY(dev_zero(err, 4, st));
-        HIP_TRY(dev_zero(gran, gran_bytes, st));
-        if (int rc = launch_resident(fn, grid, block, args, shmem, st)) return rc;
-      }
-    } else if (g.W > 1) {
-      if (int rc = launch_resident(fn, grid, block, args, shmem, st)) return rc;
-    } else {
-      HIP_TRY(hipLaunchKernel(fn, grid, block, args, shmem, st));
-    }
-    if (ev) HIP_TRY(hipEventRecord(ev[2 * ci + 1], st));
+    // between this call's chunks: the first chunk of a call checks nothing
+    const unsigned long long expect = k0 > 0 && L.ck_seq ? *L.ck_seq : 0ull;
+    HandoffCheck hc = handoff(expect, L.ck && L.ck_seq ? ++*L.ck_seq : 0ull);
+    void* args[] = {(void*)&L.jobs, (void*)&W,  (void*)&cap, (void*)&bins_cap, (void*)&nr,  (void*)&gq, (void*)&gs, (void*)&k0,
+                    (void*)&k1,   (void*)&gc, (void*)&L.err, (void*)&sp,       (void*)&nst, (void*)&X,  (void*)&epoch0,
+                    (void*)&hc,   (void*)&L.k_find};
+    if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci], st));
+    if (int rc = launch_chunk(st, L, fn, grid, shmem, args, X, xcd)) return rc;
+    if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci + 1], st));
   }
-  if (ck && ck_seq && n_pods > 0) {  // the last chunk's write-back, checked (nothing repairs it)
-    const HandoffLayout hl(g.W, n_res, max_nodes, nsc, q.pi);
-    HandoffCheck hc{};
-    hc.sum = ck;
-    hc.expect = *ck_seq;
-    hc.retries = err + 1;
-    hc.xcc = (int*)(ck + hl.o_xcc);
-    hc.diag = (long long*)(ck + hl.o_diag);
-    hc.shadow = (long long*)(ck + hl.o_shadow);
-    if (q.pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, jobs, W, sp_grid ? X.w_off : 0, n_res, hc, err);
-    else hipLaunchKernelGGL(k_handoff_final, grid, dim3(256), 0, st, jobs, W, sp_grid ? X.w_off : 0, n_res, hc, err);
+  if (L.ck && L.ck_seq && L.n_pods > 0) {  // the last chunk's write-back, checked (nothing repairs it)
+    const HandoffCheck hc = handoff(*L.ck_seq, 0ull);
+    if (q.pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
+    else hipLaunchKernelGGL(k_handoff_final, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
     HIP_TRY(hipGetLastError());
   }
   return 0;
 }
 
-// run k_schedule / k_simple / k_spread on the loaded cluster for pods [0, n); results stay on the device
 // A device range copied back with the launch's outcome (one pinned staging, one sync).
 struct ReadBack {
   const void* src = nullptr;
   size_t bytes = 0;
-  const char* host = nullptr;  // set by run_single: the bytes in pinned memory until the next call
+  const char* host = nullptr;  // set by finish_batch: the bytes in pinned memory until the next call
 };
 
 static int ensure_pinned(void*& p, size_t& cap, size_t need) {
@@ -3705,41 +3718,49 @@ static int ensure_pinned(void*& p, size_t& cap, size_t need) {
   return 0;
 }
 
-static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& dp, int n, bool commit, bool record,
-                           bool keep_norm, uint32_t flags, int32_t* chosen_out, bool staged, ReadBack* rbk,
-                           const PackedUpload* pu);
-
-// A split run that fails once its granule epochs are assigned (an exchange timed out, or the
-// launch failed) leaves this part's epochs apart from its peers': the context then refuses
-// split runs until kss_split_config re-arms it (fresh zeroed inbox, epochs from 0) — on
-// every part, with the peers exchanged again.
-static int run_single(kss_ctx* ctx, const PlanNeeds& need, const DevPods& dp, int n, bool commit, bool record,
-                      bool keep_norm, uint32_t flags, int32_t* chosen_out, bool staged = false, ReadBack* rbk = nullptr,
-                      const PackedUpload* pu = nullptr) {
-  const bool split = ctx->split_n > 1;
-  if (split && ctx->split_broken)
-    return fail(KSS_E_INVAL, "split grid: an earlier run failed; re-arm every part (kss_split_config, then the peers)");
-  const unsigned e0 = ctx->split_epoch;
-  const int rc = run_single_impl(ctx, need, dp, n, commit, record, keep_norm, flags, chosen_out, staged, rbk, pu);
-  if (rc && split && ctx->split_epoch != e0) ctx->split_broken = true;
-  return rc;
+// The automatic shard count: ~nodes_per_shard nodes per workgroup, at most one per CU; option shards fixes it.
+static int auto_shards(const kss_ctx* ctx, size_t N) {
+  if (ctx->force_w > 0) return std::min(ctx->force_w, ctx->n_cu);
+  return std::max(1, std::min(ctx->n_cu, (int)((N + ctx->nodes_per_shard - 1) / ctx->nodes_per_shard)));
 }
 
-static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& dp, int n, bool commit, bool record,
-                           bool keep_norm, uint32_t flags, int32_t* chosen_out, bool staged, ReadBack* rbk,
-                           const PackedUpload* pu) {
+// The window rules that plan_batch and kss_plan_podset_ex share: a PreFilterResult node list keeps a
+// windowed batch off the loop kernels; k_spread runs the window only under the default profile with the fold off.
+static bool window_names_block(bool windowed, bool names) { return windowed && names; }
+static bool spread_window_profile_ok(const kss_profile& p) { return !opt(O_FOLD) && same_profile(p, default_profile_c()); }
+
+// What plan_batch decides for one batch; launch_batch and finish_batch read nothing else about the route.
+struct BatchPlan {
+  Geometry g;
+  bool simple = false, simple_pi = false, simple_vol = false, spread = false;  // k_simple and its forms, k_spread
+  bool xcd_simple = false, xcd_spread = false, tab = false, flat = false;  // XCD-local grid; shape table, flat exchange
+  bool window = false, spread_win = false;  // percentageOfNodesToScore < 100; ... and k_find < N (the search can stop early)
+  int k_find = 0, win_find = 0;             // numFeasibleNodesToFind (N without a window); 0 unless k_find < N
+  int chunk = 0, n_res = 0;                 // pods per loop-kernel launch (0: k_schedule); k_spread's resident count rows
+  const GpodNeeds* q = nullptr;             // k_spread's needs: the context's, or qw under the window (so: no copies)
+  GpodNeeds qw;
+  double count_total = 0, cell_total = 0;  // the count bounds once the batch has committed
+  size_t lds = 0;                          // the loop kernel's dynamic LDS per workgroup
+  int n = 0, sched_bins = 0;  // the call's pods [0, n); k_schedule's bins (the window's per-shard counts behind the plan's)
+  bool commit = false, record = false, keep_norm = false, general = false;
+  bool loop() const { return simple || spread; }  // k_static + a persistent loop kernel
+};
+
+// launch_batch's results.  one_copy (run_single): error word, outcome (+64 B) and record slot sit at pp_err behind a per-pod upload.
+struct BatchLaunched {
+  bool one_copy = false;
+  size_t pp_err = 0, stamp_bytes = 0;
+  int* errp = nullptr;
+  unsigned long long* stamps = nullptr;  // diagnostic stamps (kss_set_stamps_file), or null
+  int n_chunks = 0;
+};
+
+// Which kernel, geometry and form pods [0, n) run on, or the refusal.  Assigns no granule epoch and writes no
+// ctx->last_* field: a refused batch leaves the context as it was.  Its only device work is vol_pack_state.
+static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, bool record, bool keep_norm, uint32_t flags,
+                      bool staged, BatchPlan& pl) {
   const size_t N = (size_t)ctx->dc.N;
-  const SlotLayout SL(N);
-  const int nslots = record ? std::max(n, 1) : 1;
-  int rc = ctx->slot_buf.ensure(SL.bytes * (size_t)nslots);
-  if (rc) return rc;
-  rc = ctx->meta_buf.ensure(sizeof(PodMeta) * (size_t)std::max(n, 1));
-  if (rc) return rc;
-  rc = ctx->chosen_buf.ensure(sizeof(int32_t) * (size_t)std::max(n, 1));
-  if (rc) return rc;
-  // shard count: ~nodes_per_shard nodes per workgroup, at most one workgroup per CU
-  int W = std::max(1, std::min(ctx->n_cu, (int)((N + ctx->nodes_per_shard - 1) / ctx->nodes_per_shard)));
-  if (ctx->force_w > 0) W = std::min(ctx->force_w, ctx->n_cu);
+  int W = auto_shards(ctx, N);
   // split grid (kss_split_config): the shard count is fixed by the parts, every part the same
   const bool split = ctx->split_n > 1;
   if (split) {
@@ -3755,16 +3776,14 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   // publish into the other epoch parity's granules)
   if (split && W != ctx->split_n * ctx->split_wl)
     return fail(KSS_E_UNSUPPORTED, "split grid: more shards than nodes (fewer shards per part)");
-  // a k_simple-eligible batch keeps W within k_simple's exchange sweep (64 * SX_CHUNKS
-  // shards): at 100k nodes, 98-128 k_simple shards beat 256 k_schedule shards (69.8k
-  // against 44.2k pods/s)
   // percentageOfNodesToScore below 100: findNodesThatPassFilters' window (numFeasibleNodesToFind,
-  // nextStartNodeIndex) runs on k_schedule only; its per-shard count exchange needs W + 1 values
-  const bool window = ctx->prof.pct_nodes_to_score < 100;
+  // nextStartNodeIndex); k_schedule's per-shard count exchange needs W + 1 values
+  const bool window = pl.window = ctx->prof.pct_nodes_to_score < 100;
   // k_simple runs the window itself (simple_sync_win) for pods without a PreFilterResult list, on
   // one part or on a split grid; k_find = N: the list is too short for a window (every node processed)
-  const int k_find = window ? num_feasible_to_find((int)N, ctx->prof.pct_nodes_to_score) : (int)N;
-  const bool simple_win_ok = !window || k_find >= (int)N || !ctx->staged_names;
+  const int k_find = pl.k_find = window ? num_feasible_to_find((int)N, ctx->prof.pct_nodes_to_score) : (int)N;
+  const bool windowed = pl.spread_win = window && k_find < (int)N;
+  pl.win_find = windowed ? k_find : 0;
   // k_schedule's window exchange: W + 1 values.  Not a split grid's limit: its W is fixed by the
   // parts and it runs a loop kernel or nothing (the loop kernels' own limits are checked below)
   if (window && !split) W = std::min(W, XW_MAX - NSCAL);
@@ -3772,41 +3791,41 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   // k_schedule only
   const bool nomq = !ctx->nom.empty();
   if (nomq && split) return fail(KSS_E_UNSUPPORTED, "split grids do not read the nominator");
-  bool simple_ok = simple_win_ok && !nomq && staged && ctx->spod_ok && commit && !record && !keep_norm && !need.general &&
-                   scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
-                   !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
+  // what both loop kernels ask (a per-pod call stops at `staged` and pays for no value check)
+  const bool loop_ok = !window_names_block(windowed, ctx->staged_names) && !nomq && staged && commit && !record && !keep_norm &&
+                       scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values &&
+                       f64_exact(ctx->f64_cluster, ctx->f64_pods, n) && !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL);
+  bool simple_ok = loop_ok && ctx->spod_ok && !need.general &&
                    // the ports-and-images form: one part, and the option still on (it is process-wide)
                    (!ctx->spod_pi || (!split && opt(O_SIMPLE_PI))) &&
                    // its volumes form: that option too, and the window only with simple_volumes_window
-                   (!ctx->spod_vol || (opt(O_SIMPLE_VOL) && (opt(O_SIMPLE_VOL_WIN) || !(window && k_find < (int)N))));
+                   (!ctx->spod_vol || (opt(O_SIMPLE_VOL) && (opt(O_SIMPLE_VOL_WIN) || !windowed)));
   // ... and the packed fields cannot overflow (vol_form_admit's condition 4) on the columns as they
   // are now: packed here, before the batch's first launch
   if (simple_ok && ctx->spod_vol) {
     bool fits = false;
-    if ((rc = vol_pack_state(ctx, fits))) return rc;
+    if (int rc = vol_pack_state(ctx, fits)) return rc;
     simple_ok = fits;
   }
+  // a k_simple-eligible batch keeps W within k_simple's exchange sweep (64 * SX_CHUNKS
+  // shards): at 100k nodes, 98-128 k_simple shards beat 256 k_schedule shards (69.8k
+  // against 44.2k pods/s)
   if (simple_ok && ctx->force_w <= 0 && !split) W = std::min(W, 64 * SX_CHUNKS);
-  // XCD-local k_simple (launch_simple xcd, xcd_slot): a cluster whose shards fit one XCD's CUs
-  // at one node per lane runs every shard on XCD 0, so the per-pod exchange stays in that
-  // XCD's L2 (KSS_XCD=0: off)
-  const int xcd_cus = ctx->n_cu / XCD_GRID_MULT;
-  const bool xcd_try = simple_ok && !split && ctx->force_w <= 0 && ctx->xcd_mode && ctx->n_cu % XCD_GRID_MULT == 0 &&
-                       !(flags & (KSS_SCHED_FORCE_SINGLE_WG | KSS_SCHED_FORCE_MULTI_WG)) &&
-                       N <= (size_t)(ctx->xcd_w > 0 ? ctx->xcd_w : xcd_cus) * PW_LANES * (KSS_MAX_THREADS / 64);
-  if (xcd_try) W = std::min(W, ctx->xcd_w > 0 ? ctx->xcd_w : xcd_cus);
+  // XCD-local grids (launch_chunk xcd, xcd_slot): a cluster whose shards fit one XCD's CUs runs every
+  // shard on XCD 0, so the per-pod exchange stays in that XCD's L2 (KSS_XCD=0: off)
+  const int xcd_w = ctx->xcd_w > 0 ? ctx->xcd_w : ctx->n_cu / XCD_GRID_MULT;
+  const bool xcd_ok = !split && ctx->force_w <= 0 && ctx->xcd_mode && ctx->n_cu % XCD_GRID_MULT == 0 &&
+                      !(flags & (KSS_SCHED_FORCE_SINGLE_WG | KSS_SCHED_FORCE_MULTI_WG));
+  // ... k_simple's at one node per lane
+  const bool xcd_try = simple_ok && xcd_ok && N <= (size_t)xcd_w * PW_LANES * (KSS_MAX_THREADS / 64);
+  if (xcd_try) W = std::min(W, xcd_w);
   // a batch with programs on k_spread: 32-bit counts and scores (spread_bounds_ok)
-  const double count_total = ctx->count_bound + (commit ? (double)n * (1.0 + ctx->staged_max_own) : 0.0);
-  const double cell_total = ctx->cell_bound + (commit ? (double)n * ctx->gneed.max_mult : 0.0);
+  pl.count_total = ctx->count_bound + (commit ? (double)n * (1.0 + ctx->staged_max_own) : 0.0);
+  pl.cell_total = ctx->cell_bound + (commit ? (double)n * ctx->gneed.max_mult : 0.0);
   // k_spread runs the window itself (spread_schedule WIN) for default-profile pods without a
   // PreFilterResult list, the statistics fold off (one part or a split grid)
-  const bool spread_win = window && k_find < (int)N;
-  const bool spread_win_ok = !spread_win || (!ctx->staged_names && !opt(O_FOLD) &&
-                                             same_profile(ctx->prof, default_profile_c()));
-  const bool spread_ok = spread_win_ok && !nomq && staged && ctx->gpod_ok && commit && !record && !keep_norm && need.general &&
-                         scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values && f64_exact(ctx->f64_cluster, ctx->f64_pods, n) &&
-                         !ctx->no_simple && !ctx->no_spread && !(flags & KSS_SCHED_GENERAL_KERNEL) &&
-                         spread_bounds_ok(ctx->gneed, count_total, cell_total, (int)N) &&
+  const bool spread_ok = loop_ok && (!windowed || spread_window_profile_ok(ctx->prof)) && ctx->gpod_ok && need.general &&
+                         !ctx->no_spread && spread_bounds_ok(ctx->gneed, pl.count_total, pl.cell_total, (int)N) &&
                          // the ports-and-images form: one part, no fold, and the option still on (it is process-wide)
                          (!ctx->gpod_pi || (!split && opt(O_SPREAD_PI) && !opt(O_FOLD)));
   if (opt(O_TRACE_PATH))  // diagnosis: why a batch with programs is (not) on k_spread
@@ -3815,8 +3834,8 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
             "(ref_weight=%lld total=%.0f cell=%.0f) n_res=%zu bins=%d\n",
             (int)staged, (int)ctx->gpod_ok, (int)commit, (int)record, (int)need.general, ctx->dc.n_scalar,
             (int)ctx->small_values, (int)f64_exact(ctx->f64_cluster, ctx->f64_pods, n),
-            (int)spread_bounds_ok(ctx->gneed, count_total, cell_total, (int)N), (long long)ctx->gneed.ref_weight,
-            count_total, cell_total, ctx->gneed.res_rows.size(), ctx->gneed.bins_cap);
+            (int)spread_bounds_ok(ctx->gneed, pl.count_total, pl.cell_total, (int)N), (long long)ctx->gneed.ref_weight,
+            pl.count_total, pl.cell_total, ctx->gneed.res_rows.size(), ctx->gneed.bins_cap);
   const int w_min = (int)((N + KSS_MAX_NPT * KSS_MAX_THREADS - 1) / (KSS_MAX_NPT * KSS_MAX_THREADS));
   if (split && W < w_min) return fail(KSS_E_UNSUPPORTED, "split grid: too few shards for this cluster");
   W = std::max(W, w_min);
@@ -3826,105 +3845,109 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   }
   if (!split && W > ctx->n_cu) return fail(KSS_E_UNSUPPORTED, "cluster too large for one device");
   if (split && ctx->split_wl > ctx->n_cu) return fail(KSS_E_UNSUPPORTED, "split grid: more shards per part than CUs");
-  Geometry g;
+  Geometry& g = pl.g;
   if (!pick_geometry((int)N, W, ctx->pref_threads, g)) return fail(KSS_E_UNSUPPORTED, "no geometry for this cluster");
-  const bool simple = simple_ok && simple_fits(g, ctx->dc.n_scalar, ctx->spod_pi, ctx->spod_vol);
-  const bool simple_pi = simple && ctx->spod_pi;
-  const bool simple_vol = simple && ctx->spod_vol;
-  const int n_res = (int)ctx->gneed.res_rows.size();
-  bool spread = spread_ok && spread_fits(g, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar);
+  const int nsc = ctx->dc.n_scalar;
+  const bool simple = pl.simple = simple_ok && simple_fits(g, nsc, ctx->spod_pi, ctx->spod_vol);
+  pl.simple_pi = simple && ctx->spod_pi, pl.simple_vol = simple && ctx->spod_vol;
+  const int n_res = pl.n_res = (int)ctx->gneed.res_rows.size();
+  pl.q = &ctx->gneed;
+  auto fits = [&](const Geometry& g2) { return spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, nsc); };
+  bool spread = spread_ok && fits(g);
   if (spread && !simple && opt(O_THREADS) <= 0 && opt(O_FORCE_THREADS) <= 0) {
     // k_spread: one node per lane where the workgroup allows it (up to SPREAD_PREF_THREADS):
     // its per-node passes are the chain between exchanges (C4: 256 -> 512 lanes, stats +
     // filter + normalise 4.4 -> 2.6 us per pod)
     Geometry g2;
-    if (pick_geometry((int)N, W, SPREAD_PREF_THREADS, g2) && g2.threads > g.threads &&
-        spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar))
-      g = g2;
+    if (pick_geometry((int)N, W, SPREAD_PREF_THREADS, g2) && g2.threads > g.threads && fits(g2)) g = g2;
   }
   if (split && simple && g.W > 64 * SX_CHUNKS) return fail(KSS_E_UNSUPPORTED, "split grid: k_simple sweeps at most 128 shards");
   if (spread_ok && !spread && g.threads < KSS_MAX_THREADS) {  // more prefetch lanes per shard
     Geometry g2 = g;
-    const int per = (int)((N + g.W - 1) / g.W);
     g2.threads = KSS_MAX_THREADS;
-    g2.npt = (per + KSS_MAX_THREADS - 1) / KSS_MAX_THREADS;
-    if (spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar)) {
-      g = g2;
-      spread = true;
-    }
+    g2.npt = ((int)((N + g.W - 1) / g.W) + KSS_MAX_THREADS - 1) / KSS_MAX_THREADS;
+    if ((spread = fits(g2))) g = g2;
   }
   // more shards when the resident count rows of a shard exceed its LDS (not when the caller
   // fixed the shard count)
+  auto repick = [&](int W2, int pref) {
+    Geometry g2;
+    if (!pick_geometry((int)N, W2, pref, g2) || !fits(g2)) return false;
+    g = g2;
+    return true;
+  };
   for (int W2 = g.W * 2; spread_ok && !spread && ctx->force_w <= 0 && !split && !(flags & KSS_SCHED_FORCE_SINGLE_WG) &&
                          W2 <= ctx->n_cu && W2 <= (int)N;
-       W2 *= 2) {
-    Geometry g2;
-    if (pick_geometry((int)N, W2, ctx->pref_threads, g2) && spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar)) {
-      g = g2;
-      spread = true;
-    }
-  }
+       W2 *= 2)
+    spread = repick(W2, ctx->pref_threads);
   if (!spread && g.W > 1 && need.xw > XW_MAX) {  // k_schedule after all: its exchange payload needs one workgroup
     if (w_min > 1) return fail(KSS_E_UNSUPPORTED, "topology histograms too large for a sharded cluster");
     if (!pick_geometry((int)N, 1, ctx->pref_threads, g)) return fail(KSS_E_UNSUPPORTED, "no geometry for this cluster");
   }
-  // XCD-local k_spread (launch_spread xcd): the shards on one XCD when they fit its CUs
-  bool xcd_spread = false;
-  if (spread && !simple && !split && ctx->force_w <= 0 && ctx->xcd_mode && ctx->n_cu % XCD_GRID_MULT == 0 &&
-      !(flags & (KSS_SCHED_FORCE_SINGLE_WG | KSS_SCHED_FORCE_MULTI_WG))) {
-    const int xw = ctx->xcd_w > 0 ? ctx->xcd_w : xcd_cus;
-    Geometry g2;
-    if (g.W > 1 && g.W <= xw) {
-      xcd_spread = true;
-    } else if (g.W > xw && pick_geometry((int)N, xw, SPREAD_PREF_THREADS, g2) &&
-               spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar)) {
-      g = g2;
-      xcd_spread = true;
-    }
-  }
-  const bool loop = simple || spread;  // k_static + a persistent loop kernel
-  if (split && !loop)
+  // XCD-local k_spread: the shards on one XCD when they fit its CUs
+  if (spread && !simple && xcd_ok) pl.xcd_spread = g.W > xcd_w ? repick(xcd_w, SPREAD_PREF_THREADS) : g.W > 1;
+  pl.spread = spread, pl.xcd_simple = simple && xcd_try && g.W > 1;
+  if (split && !pl.loop())
     return fail(KSS_E_UNSUPPORTED, spread_ok ? "split grid: a k_spread shard exceeds LDS (more shards per part)"
                                              : "split grid: the batch needs k_schedule (kss_plan_podset)");
-  // The window on a split grid, before any epoch is assigned: the limits of the loop kernels' own
-  // window exchanges (k_simple's sweep of 64 * SX_CHUNKS shards is refused above).
-  const int win_find = k_find < (int)N ? k_find : 0;
-  if (split && win_find > 0) {
+  // the window on k_spread: the count exchange's W SUM values behind the pod's bins and one scalar
+  if (spread && windowed) {
+    pl.qw = ctx->gneed;
+    pl.qw.bins_cap += g.W;
+    pl.qw.xw = std::max(pl.qw.xw, g.W + 1);
+    pl.q = &pl.qw;
+  }
+  // The window on a split grid: the limits of the loop kernels' own window exchanges (k_simple's sweep
+  // of 64 * SX_CHUNKS shards is refused above).
+  if (split && windowed) {
     const size_t half = ctx->split_inbox_bytes / 2 / sizeof(unsigned long long);
     if (simple) {
       // statistics granules of both epoch parities, the cut granules, the end-of-launch cursor granule
       if (sxw_words(g.W) > half) return fail(KSS_E_UNSUPPORTED, "split grid: k_simple's window granules exceed an inbox half");
     } else {
-      // the count exchange: W SUM values behind the pod's bins and one scalar, per shard and parity
-      GpodNeeds qw = ctx->gneed;
-      qw.bins_cap += g.W;
-      qw.xw = std::max(qw.xw, g.W + 1);
+      // the count exchange, per shard and parity
       if (g.W + 1 > G_XW) return fail(KSS_E_UNSUPPORTED, "split grid: k_spread's window count vector exceeds G_XW values (fewer shards)");
-      if (2 * (size_t)g.W * (size_t)qw.gs() > half)
+      if (2 * (size_t)g.W * (size_t)pl.qw.gs() > half)
         return fail(KSS_E_UNSUPPORTED, "split grid: k_spread's window count vector exceeds an inbox half");
-      if (!spread_fits(g, qw, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar))
+      if (!spread_fits(g, pl.qw, ctx->dc.n_keys, n_res, N, nsc))
         return fail(KSS_E_UNSUPPORTED, "split grid: k_spread's window count bins exceed LDS (more shards per part)");
     }
   }
-  const int chunk = loop ? static_chunk(N, n) : 0;
+  pl.chunk = pl.loop() ? static_chunk(N, n) : 0;
+  // the shape table: the whole staged batch (its shape directory sits in its first records)
+  // (the ports-and-images form: an image-only batch, option table_images -- k_simple_tab_pi;
+  // UsedPorts is not a function of the resource shape, so a host-port pod keeps the batch on k_simple_pi)
+  // (the volumes form: never -- its batches have no shapes)
+  pl.tab = simple && !pl.simple_vol && (!pl.simple_pi || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
+           n == ctx->staged_n && shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, pl.win_find, nsc);
+  pl.flat = pl.tab && flat_exchange_ok(g, (int)N, ctx->prof, split);
+  if (simple) pl.lds = simple_lds(simple_cap(g), nsc, pl.simple_pi, pl.simple_vol, pl.tab ? ctx->spod_shapes : 0);
+  if (spread) pl.lds = spread_lds(g, *pl.q, ctx->dc.n_keys, n_res, N, nsc);
+  pl.n = n, pl.commit = commit, pl.record = record, pl.keep_norm = keep_norm;
+  pl.general = need.general, pl.sched_bins = std::max(need.bins_cap, 0) + (window ? g.W : 0);
+  return 0;
+}
+
+// The planned batch onto the stream: job, granules and epochs, stamps and events, the one launcher call.
+static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, const PackedUpload* pu, BatchLaunched& run) {
+  const size_t N = (size_t)ctx->dc.N;
+  const Geometry& g = pl.g;
+  const int n = pl.n, chunk = pl.chunk;
+  const bool simple = pl.simple, spread = pl.spread, loop = pl.loop(), split = ctx->split_n > 1;
+  int rc = 0;
   if (loop && (rc = ctx->stat_buf.ensure(sizeof(uint32_t) * (size_t)chunk * std::max<size_t>(N, 1)))) return rc;
   DevJob job{};
   job.c = ctx->dc;
   job.P = dp;
   job.n_pods = n;
-  job.commit = commit ? 1 : 0;
-  job.keep_norm = keep_norm ? 1 : 0;
-  job.record = record ? 1 : 0;
+  job.commit = pl.commit, job.keep_norm = pl.keep_norm, job.record = pl.record;
   job.slots = (uint8_t*)ctx->slot_buf.p;
-  job.slot_bytes = SL.bytes;
+  job.slot_bytes = SlotLayout(N).bytes;
   job.chosen = (int32_t*)ctx->chosen_buf.p;
   job.meta = (PodMeta*)ctx->meta_buf.p;
-  // per-pod calls: error word, outcome and record slot contiguous behind the uploaded image,
-  // so the whole read-back is one copy
-  const bool one_copy = pu && pu->slot && n == 1 && !chosen_out;
-  const size_t pp_err = pu ? pu->extra_off + align_up(sizeof(DevJob), 16) : 0, pp_meta = pp_err + 64;
-  if (one_copy) {
-    job.meta = (PodMeta*)(pu->dev + pp_meta);
+  run.pp_err = pu ? pu->extra_off + align_up(sizeof(DevJob), 16) : 0;  // the outcome 64 B further
+  if (run.one_copy) {
+    job.meta = (PodMeta*)(pu->dev + run.pp_err + 64);
     job.slots = (uint8_t*)pu->slot;
   }
   job.spods = simple ? (const SPod*)ctx->spod_buf.p : nullptr;
@@ -3933,7 +3956,7 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   job.res_rows = spread ? (const int32_t*)ctx->res_buf.p : nullptr;
   job.trace = GTrace{nullptr, nullptr};
   job.cursor = (int32_t*)ctx->cursor_buf.p;
-  if (nomq) {
+  if (!ctx->nom.empty()) {
     if (ctx->nom_dirty) {
       if ((rc = ctx->nom_buf.ensure(sizeof(DevNom) * ctx->nom.size()))) return rc;
       HIP_TRY(hipMemcpyAsync(ctx->nom_buf.p, ctx->nom.data(), sizeof(DevNom) * ctx->nom.size(), hipMemcpyHostToDevice,
@@ -3956,15 +3979,13 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
   }
 #endif
   job.prof = ctx->prof;
-  rc = ctx->job_buf.ensure(sizeof(DevJob));
-  if (rc) return rc;
-  rc = ctx->err_buf.ensure(16);
-  if (rc) return rc;
+  if ((rc = ctx->job_buf.ensure(sizeof(DevJob))) || (rc = ctx->err_buf.ensure(16))) return rc;
   unsigned long long* gran = nullptr;
   // k_spread on one part: the two-level exchanges' area behind the granules (launch_spread); a
   // split grid's inbox holds the granules alone
   const size_t gb = sizeof(unsigned long long) *
                     (2 * (size_t)g.W * std::max(2 * XW_MAX, G_XW) + (spread && !split ? tl_words(g.W) : 0));
+  const int n_chunks = run.n_chunks = loop ? (n + chunk - 1) / std::max(chunk, 1) : 0;
   unsigned epoch0 = 0;
   SplitRun srun;
   if (split) {  // the local inbox, never cleared: this run's epochs start above every earlier tag
@@ -3972,19 +3993,16 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
     gran = (unsigned long long*)ctx->split_inbox;
     srun.half_words = ctx->split_inbox_bytes / 2 / sizeof(unsigned long long);
     srun.chunk0 = ctx->split_chunks;
-    ctx->split_chunks += (unsigned long long)((n + chunk - 1) / std::max(chunk, 1));
-    srun.X.n = ctx->split_n;
-    srun.X.w_off = ctx->split_part * ctx->split_wl;
-    srun.X.wl = ctx->split_wl;
+    ctx->split_chunks += (unsigned long long)n_chunks;
+    srun.X.n = ctx->split_n, srun.X.w_off = ctx->split_part * ctx->split_wl, srun.X.wl = ctx->split_wl;
     for (int i = 0; i < ctx->split_n; i++) srun.X.inbox[i] = ctx->split_peer[i];
     srun.epoch0 = ctx->split_epoch;
-    const unsigned span = (unsigned)((n + chunk - 1) / std::max(chunk, 1) + 1) * chunk_span(chunk) + 16u;
+    const unsigned span = (unsigned)(n_chunks + 1) * chunk_span(chunk) + 16u;
     if ((uint64_t)ctx->split_epoch + span >= (1ull << 31)) return fail(KSS_E_RANGE, "split grid: granule epochs exhausted");
     ctx->split_epoch += span;
   } else if (g.W > 1) {
     const void* before = ctx->gran_buf.p;
-    rc = ctx->gran_buf.ensure(gb);
-    if (rc) return rc;
+    if ((rc = ctx->gran_buf.ensure(gb))) return rc;
     gran = (unsigned long long*)ctx->gran_buf.p;
     // k_schedule after k_schedule continues the epochs (a stale tag never equals a new epoch);
     // the loop kernels restart theirs, so they, a fresh buffer, or a near-wrap clear it
@@ -3998,180 +4016,181 @@ static int run_single_impl(kss_ctx* ctx, const PlanNeeds& need, const DevPods& d
     }
     ctx->gran_epoch = loop ? 0 : epoch0 + span;
   }
-  int* errp = (int*)ctx->err_buf.p;
-  if (pu) {
-    errp = (int*)(pu->dev + pu->extra_off + align_up(sizeof(DevJob), 16));  // zero in the upload image
-    std::memset(pu->host + pu->extra_off + align_up(sizeof(DevJob), 16), 0, 16);
-  } else {
-    HIP_TRY(dev_zero(ctx->err_buf.p, 16, ctx->stream));
-  }
+  int* errp = run.errp = pu ? (int*)(pu->dev + run.pp_err) : (int*)ctx->err_buf.p;
   const DevJob* jd = (const DevJob*)ctx->job_buf.p;
-  if (pu) {  // the job rides in the per-pod call's single upload
+  if (pu) {  // the job and the zeroed error word ride in the per-pod call's single upload
+    std::memset(pu->host + run.pp_err, 0, 16);
     std::memcpy(pu->host + pu->extra_off, &job, sizeof(DevJob));
     HIP_TRY(hipMemcpyAsync(pu->dev, pu->host, pu->bytes, hipMemcpyHostToDevice, ctx->stream));
     jd = (const DevJob*)(pu->dev + pu->extra_off);
   } else {
+    HIP_TRY(dev_zero(ctx->err_buf.p, 16, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->job_buf.p, &job, sizeof(DevJob), hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-  unsigned long long* stamps = nullptr;
   // k_schedule: shard 0 only; k_simple: every shard (arrival skew of the exchanges)
-  const size_t stamp_bytes = sizeof(unsigned long long) * 8 * KSS_NSTAMP_PODS * (loop ? g.W : 1);
+  run.stamp_bytes = sizeof(unsigned long long) * 8 * KSS_NSTAMP_PODS * (loop ? g.W : 1);
   if (ctx->stamps_file) {
-    if ((rc = ctx->stamp_buf.ensure(stamp_bytes))) return rc;
-    stamps = (unsigned long long*)ctx->stamp_buf.p;
-    HIP_TRY(dev_zero(stamps, stamp_bytes, ctx->stream));
+    if ((rc = ctx->stamp_buf.ensure(run.stamp_bytes))) return rc;
+    run.stamps = (unsigned long long*)ctx->stamp_buf.p;
+    HIP_TRY(dev_zero(run.stamps, run.stamp_bytes, ctx->stream));
   }
-  const int n_chunks = loop ? (n + chunk - 1) / std::max(chunk, 1) : 0;
   while ((int)ctx->loop_ev.size() < 2 * n_chunks) {
     hipEvent_t e;
     HIP_TRY(hipEventCreate(&e));
     ctx->loop_ev.push_back(e);
   }
-  ctx->last_xcd[0] = (simple && xcd_try && g.W > 1) || xcd_spread ? 1 : 0;
-  ctx->last_lds = 0;
-  ctx->last_xcd[1] = 0;
-  // the shape table: the whole staged batch (its shape directory sits in its first records)
-  // (the ports-and-images form: an image-only batch, option table_images -- k_simple_tab_pi;
-  // UsedPorts is not a function of the resource shape, so a host-port pod keeps the batch on k_simple_pi)
-  // (the volumes form: never -- its batches have no shapes)
-  const bool tab = simple && !simple_vol && (!simple_pi || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
-                   n == ctx->staged_n &&
-                   shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, win_find, ctx->dc.n_scalar);
-  ctx->last_shape[0] = tab ? ctx->spod_shapes : 0;
-  ctx->last_shape[1] = tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
-  const bool flat = tab && flat_exchange_ok(g, (int)N, ctx->prof, split);
-  ctx->last_flat[0] = flat ? 1 : 0;
-  ctx->last_flat[1] = flat ? g.W * (g.threads / 64) : 0;
-  ctx->last_simple_form[0] = simple_vol ? 1 : 0;
-  ctx->last_simple_form[1] = !simple ? 0
-                             : (int)(tab          ? simple_lds_bytes(simple_cap(g), 0, ctx->spod_shapes)
-                                     : simple_vol ? simple_lds_bytes_vol(simple_cap(g), ctx->dc.n_scalar)
-                                     : simple_pi  ? simple_lds_bytes_pi(simple_cap(g), ctx->dc.n_scalar)
-                                                  : simple_lds_bytes(simple_cap(g), ctx->dc.n_scalar));
-  if (simple)
-    rc = launch_simple(ctx->stream, g, 1, jd, ctx->prof, n, (int)N, chunk, gran, gb,
-                       errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr, ctx->dc.n_scalar, ctx->last_xcd[0] != 0,
-                       &ctx->last_xcd[1], ctx->dc.n_keys, nullptr, nullptr, win_find, tab ? ctx->spod_shapes : 0, flat,
-                       simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr, nullptr,
-                       simple_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr);
-  else if (spread)
-  {
-    const HandoffLayout hl(g.W, n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi);
-    if ((rc = ctx->ck_buf.ensure(sizeof(unsigned long long) * hl.words))) return rc;
-    HIP_TRY(dev_zero((unsigned long long*)ctx->ck_buf.p + hl.o_diag, sizeof(unsigned long long), ctx->stream));
-    ctx->ck_diag_off = hl.o_diag;
-    // the window's count exchange: W SUM values behind the pod's bins, one scalar
-    GpodNeeds qw = ctx->gneed;
-    if (spread_win) {
-      qw.bins_cap += g.W;
-      qw.xw = std::max(qw.xw, g.W + 1);
+  // what the kss_last_* calls report, from the plan (last_kernel: once the launch is queued)
+  ctx->last_xcd[0] = pl.xcd_simple || pl.xcd_spread ? 1 : 0, ctx->last_xcd[1] = 0;
+  ctx->last_lds = 0;  // (k_spread's: once its hand-off buffer stands)
+  ctx->last_shape[0] = pl.tab ? ctx->spod_shapes : 0;
+  ctx->last_shape[1] = pl.tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
+  ctx->last_flat[0] = pl.flat ? 1 : 0, ctx->last_flat[1] = pl.flat ? g.W * (g.threads / 64) : 0;
+  ctx->last_simple_form[0] = pl.simple_vol ? 1 : 0, ctx->last_simple_form[1] = simple ? (int)pl.lds : 0;
+  if (!loop) {
+    rc = launch_schedule(ctx->stream, g, 1, pl.sched_bins, pl.general, ctx->dc.n_keys, jd, ctx->prof, gran, errp, run.stamps,
+                         epoch0);
+  } else {
+    LoopLaunch L;  // what both loop kernels take
+    L.g = g;
+    L.jobs = jd;
+    L.prof = &ctx->prof;
+    L.n_pods = n, L.max_nodes = (int)N, L.chunk = chunk;
+    L.n_keys = ctx->dc.n_keys, L.nsc = ctx->dc.n_scalar;
+    L.gran = gran, L.gran_bytes = gb, L.stamps = run.stamps;
+    L.err = errp;
+    L.ev = ctx->loop_ev.data();
+    L.split = split ? &srun : nullptr;
+    L.xcd = pl.xcd_simple || pl.xcd_spread, L.xcd_fallbacks = &ctx->last_xcd[1];
+    L.k_find = pl.win_find;
+    if (simple) {
+      SimpleLaunch S{L};
+      S.n_shapes = pl.tab ? ctx->spod_shapes : 0;
+      S.flat = pl.flat;
+      S.sports = pl.simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr;
+      S.vl = pl.simple_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
+      rc = launch_simple(ctx->stream, S);
+    } else {
+      const HandoffLayout hl(g.W, pl.n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi);
+      if ((rc = ctx->ck_buf.ensure(sizeof(unsigned long long) * hl.words))) return rc;
+      HIP_TRY(dev_zero((unsigned long long*)ctx->ck_buf.p + hl.o_diag, sizeof(unsigned long long), ctx->stream));
+      ctx->ck_diag_off = hl.o_diag;
+      ctx->last_lds = (long long)pl.lds;
+      SpreadLaunch G{L};
+      G.q = pl.q, G.n_res = pl.n_res;
+      G.ck = (unsigned long long*)ctx->ck_buf.p, G.ck_seq = &ctx->ck_seq;
+      rc = launch_spread(ctx->stream, G);
     }
-    ctx->last_lds = (long long)spread_lds(g, qw, ctx->dc.n_keys, n_res, N, ctx->dc.n_scalar);
-    rc = launch_spread(ctx->stream, g, qw, ctx->dc.n_keys, n_res, jd, ctx->prof, n,
-                       (int)N, chunk, gran, gb, errp, stamps, ctx->loop_ev.data(), split ? &srun : nullptr,
-                       (unsigned long long*)ctx->ck_buf.p, &ctx->ck_seq, ctx->dc.n_scalar, xcd_spread, &ctx->last_xcd[1],
-                       spread_win ? k_find : 0);
   }
-  else  // window: the per-shard feasible counts sit behind the plan's bins
-    rc = launch_schedule(ctx->stream, g, 1, std::max(need.bins_cap, 0) + (window ? g.W : 0), need.general, ctx->dc.n_keys,
-                         jd, ctx->prof, gran, errp, stamps, epoch0);
   if (rc) return rc;
   ctx->last_kernel = simple ? 1 : (spread ? 2 : 0);
   HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  // diagnostic stamps -> KSS_STAMPS_FILE, one record per launch: {kernel (0 k_schedule,
-  // 1 k_simple, 2 k_spread), shards} then the stamps
-  auto dump_stamps = [&]() -> int {
-    if (!stamps) return 0;
-    std::vector<unsigned long long> h(2 + stamp_bytes / 8);
-    h[0] = simple ? 1 : (spread ? 2 : 0);
-    h[1] = loop ? (unsigned long long)g.W : 1;
-    HIP_TRY(hipMemcpy(h.data() + 2, stamps, stamp_bytes, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(ctx->stamps_file, "ab")) {
-      fwrite(h.data(), 8, h.size(), f);
-      fclose(f);
-    }
-    return 0;
-  };
-  if (one_copy) {  // [error word .. outcome .. record slot up to the requested span]: one copy, one sync
-    const size_t span = (size_t)(pu->slot - (pu->dev + pp_err)) + (rbk ? rbk->bytes : 0);
-    if ((rc = ensure_pinned(ctx->rb, ctx->rb_cap, span))) return rc;
-    char* hb = (char*)ctx->rb;
-    HIP_TRY(hipMemcpyAsync(hb, pu->dev + pp_err, span, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ctx->last_loop_ms = ms;
-    ctx->last_launches = 1;
-    ctx->last_geom[0] = g.W;
-    ctx->last_geom[1] = g.threads;
-    ctx->last_geom[2] = g.npt;
-    int errw = 0;
-    std::memcpy(&errw, hb, sizeof(int));
-    if (errw) return fail(KSS_E_DEVICE, "shard exchange timed out (workgroups not co-resident?)");
-    ctx->meta_host.resize(1);
-    std::memcpy(ctx->meta_host.data(), hb + (pp_meta - pp_err), sizeof(PodMeta));
-    if (rbk) rbk->host = hb + (pu->slot - (pu->dev + pp_err));
-    ctx->recorded = 0;  // the record went to the caller; kss_fetch_record has nothing to serve
-    ctx->meta_n = 1;
-    ctx->axis_meta_dirty = false;
-    return dump_stamps();
-  }
-  // every read-back of the launch into one pinned staging, then one synchronisation
+  return 0;
+}
+
+// The read-back (one pinned staging, one synchronisation), then the context's view of the run.
+static int finish_batch(kss_ctx* ctx, const BatchPlan& pl, const BatchLaunched& run, int32_t* chosen_out, ReadBack* rbk,
+                        const PackedUpload* pu) {
+  const int n = pl.n;
   const size_t mb = sizeof(PodMeta) * (size_t)std::max(n, 1), cb = chosen_out && n ? sizeof(int32_t) * (size_t)n : 0;
-  const size_t o_meta = 16, o_chosen = align_up(o_meta + mb, 16), o_rb = align_up(o_chosen + cb, 16);
-  if ((rc = ensure_pinned(ctx->rb, ctx->rb_cap, o_rb + (rbk ? rbk->bytes : 0)))) return rc;
+  const size_t rb = rbk ? rbk->bytes : 0;
+  // a per-pod call's image holds [error word .. outcome .. record slot up to the requested span]: one copy
+  const size_t o_meta = run.one_copy ? 64 : 16, o_chosen = align_up(o_meta + mb, 16);
+  const size_t o_rb = run.one_copy ? (size_t)(pu->slot - (pu->dev + run.pp_err)) : align_up(o_chosen + cb, 16);
+  if (int rc = ensure_pinned(ctx->rb, ctx->rb_cap, o_rb + rb)) return rc;
   char* hb = (char*)ctx->rb;
-  HIP_TRY(hipMemcpyAsync(hb, errp, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(hb + o_meta, ctx->meta_buf.p, mb, hipMemcpyDeviceToHost, ctx->stream));
-  if (cb) HIP_TRY(hipMemcpyAsync(hb + o_chosen, ctx->chosen_buf.p, cb, hipMemcpyDeviceToHost, ctx->stream));
-  if (rbk && rbk->bytes) HIP_TRY(hipMemcpyAsync(hb + o_rb, rbk->src, rbk->bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (run.one_copy) {
+    HIP_TRY(hipMemcpyAsync(hb, pu->dev + run.pp_err, o_rb + rb, hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(hb, run.errp, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hb + o_meta, ctx->meta_buf.p, mb, hipMemcpyDeviceToHost, ctx->stream));
+    if (cb) HIP_TRY(hipMemcpyAsync(hb + o_chosen, ctx->chosen_buf.p, cb, hipMemcpyDeviceToHost, ctx->stream));
+    if (rb) HIP_TRY(hipMemcpyAsync(hb + o_rb, rbk->src, rb, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (rbk) rbk->host = hb + o_rb;
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->last_ms = ms;
-  ctx->last_launches = loop ? 2 * n_chunks : 1;
-  ctx->last_loop_ms = loop ? 0.0 : ms;
-  for (int i = 0; i < n_chunks; i++) {
+  ctx->last_launches = pl.loop() ? 2 * run.n_chunks : 1;
+  ctx->last_loop_ms = pl.loop() ? 0.0 : ms;
+  for (int i = 0; i < run.n_chunks; i++) {
     float t = 0;
     HIP_TRY(hipEventElapsedTime(&t, ctx->loop_ev[2 * i], ctx->loop_ev[2 * i + 1]));
     ctx->last_loop_ms += t;
   }
-  ctx->last_geom[0] = g.W;
-  ctx->last_geom[1] = g.threads;
-  ctx->last_geom[2] = g.npt;
+  ctx->last_geom[0] = pl.g.W;
+  ctx->last_geom[1] = pl.g.threads;
+  ctx->last_geom[2] = pl.g.npt;
   int errw = 0;
   std::memcpy(&errw, hb, sizeof(int));
-  std::memcpy(&ctx->last_handoff_retries, hb + sizeof(int), sizeof(int));
-  std::memcpy(&ctx->last_handoff_recovered, hb + 2 * sizeof(int), sizeof(int));
-  std::memcpy(&ctx->last_handoff_final, hb + 3 * sizeof(int), sizeof(int));
-  ctx->last_kernel_spread = spread;
-  if (errw && commit) {  // bounds as if every pod committed (upper bounds stay safe); log unknown
-    ctx->count_bound = count_total;
-    ctx->cell_bound = std::max(ctx->cell_bound, cell_total);
+  if (!run.one_copy) {  // (a per-pod call runs k_schedule: no hand-off to report)
+    std::memcpy(&ctx->last_handoff_retries, hb + sizeof(int), sizeof(int));
+    std::memcpy(&ctx->last_handoff_recovered, hb + 2 * sizeof(int), sizeof(int));
+    std::memcpy(&ctx->last_handoff_final, hb + 3 * sizeof(int), sizeof(int));
+    ctx->last_kernel_spread = pl.spread;
+  }
+  auto commit_bounds = [&] {  // as if every pod committed (upper bounds stay safe)
+    ctx->count_bound = pl.count_total;
+    ctx->cell_bound = std::max(ctx->cell_bound, pl.cell_total);
     f64_commit(ctx->f64_cluster, (double)n * ctx->f64_pods.max_creq, (double)n * ctx->f64_pods.max_cnz);
+  };
+  if (errw && pl.commit) {  // ... and the log unknown
+    commit_bounds();
     ctx->state_unknown = true;
   }
-  if (errw == 2)
+  if (errw == 2 && !run.one_copy)
     return fail(KSS_E_DEVICE, ctx->last_handoff_final ? "the last chunk's node-state write-back failed its final check"
                                                        : "node state handed between chunk launches failed its check");
   if (errw) return fail(KSS_E_DEVICE, "shard exchange timed out (workgroups not co-resident?)");
-  if (commit) {
-    ctx->count_bound = count_total;
-    ctx->cell_bound = std::max(ctx->cell_bound, cell_total);
-    f64_commit(ctx->f64_cluster, (double)n * ctx->f64_pods.max_creq, (double)n * ctx->f64_pods.max_cnz);
-  }
+  if (pl.commit) commit_bounds();
   ctx->meta_host.resize((size_t)std::max(n, 1));
   std::memcpy(ctx->meta_host.data(), hb + o_meta, mb);
   if (cb) std::memcpy(chosen_out, hb + o_chosen, cb);
-  ctx->recorded = record ? n : (n > 0 && !loop ? 1 : 0);
+  // (one copy: the record went to the caller; kss_fetch_record has nothing to serve)
+  ctx->recorded = run.one_copy ? 0 : pl.record ? n : (n > 0 && !pl.loop() ? 1 : 0);
   ctx->meta_n = n;
   ctx->axis_meta_dirty = false;
-  return dump_stamps();
+  if (!run.stamps) return 0;
+  // diagnostic stamps -> KSS_STAMPS_FILE, one record per launch: {kernel (0 k_schedule,
+  // 1 k_simple, 2 k_spread), shards} then the stamps
+  std::vector<unsigned long long> h(2 + run.stamp_bytes / 8);
+  h[0] = pl.simple ? 1 : (pl.spread ? 2 : 0);
+  h[1] = pl.loop() ? (unsigned long long)pl.g.W : 1;
+  HIP_TRY(hipMemcpy(h.data() + 2, run.stamps, run.stamp_bytes, hipMemcpyDeviceToHost));
+  if (FILE* f = fopen(ctx->stamps_file, "ab")) {
+    fwrite(h.data(), 8, h.size(), f);
+    fclose(f);
+  }
+  return 0;
 }
 
-// The volumes form before a batch's first launch (run_single; the staged batch is of the form):
+// run k_schedule / k_simple / k_spread on the loaded cluster for pods [0, n); results stay on the device.
+// A split run that fails once its granule epochs are assigned (an exchange timed out, or the
+// launch failed) leaves this part's epochs apart from its peers': the context then refuses
+// split runs until kss_split_config re-arms it (fresh zeroed inbox, epochs from 0) — on
+// every part, with the peers exchanged again.
+static int run_single(kss_ctx* ctx, const PlanNeeds& need, const DevPods& dp, int n, bool commit, bool record,
+                      bool keep_norm, uint32_t flags, int32_t* chosen_out, bool staged = false, ReadBack* rbk = nullptr,
+                      const PackedUpload* pu = nullptr) {
+  const bool split = ctx->split_n > 1;
+  if (split && ctx->split_broken)
+    return fail(KSS_E_INVAL, "split grid: an earlier run failed; re-arm every part (kss_split_config, then the peers)");
+  const unsigned e0 = ctx->split_epoch;
+  BatchPlan pl;
+  BatchLaunched run;
+  run.one_copy = pu && pu->slot && n == 1 && !chosen_out;
+  int rc = ctx->slot_buf.ensure(SlotLayout((size_t)ctx->dc.N).bytes * (size_t)(record ? std::max(n, 1) : 1));
+  if (!rc) rc = ctx->meta_buf.ensure(sizeof(PodMeta) * (size_t)std::max(n, 1));
+  if (!rc) rc = ctx->chosen_buf.ensure(sizeof(int32_t) * (size_t)std::max(n, 1));
+  if (!rc) rc = plan_batch(ctx, need, n, commit, record, keep_norm, flags, staged, pl);
+  if (!rc) rc = launch_batch(ctx, pl, dp, pu, run);
+  if (!rc) rc = finish_batch(ctx, pl, run, chosen_out, rbk, pu);
+  if (rc && split && ctx->split_epoch != e0) ctx->split_broken = true;
+  return rc;
+}
+
+// The volumes form before a batch's first launch (plan_batch; the staged batch is of the form):
 // the node-state columns packed from the device's vol_count / vol_attached / vol_limit as they are
 // now (k_vol_pack), the launch block uploaded, and vol_form_admit's condition 4 on the maxima the
 // pack reports -- one small read-back and one synchronisation, paid by a batch of the form only.
@@ -4832,8 +4851,7 @@ static int svc_start_locked(kss_ctx* ctx) {
   HIP_TRY(hipSetDevice(ctx->cfg.device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));  // every earlier launch / copy on the ctx stream is done
   const size_t N = (size_t)ctx->dc.N;
-  int W = std::max(1, std::min(ctx->n_cu, (int)((N + ctx->nodes_per_shard - 1) / ctx->nodes_per_shard)));
-  if (ctx->force_w > 0) W = std::min(ctx->force_w, ctx->n_cu);
+  int W = auto_shards(ctx, N);
   W = std::max(W, (int)((N + KSS_MAX_NPT * KSS_MAX_THREADS - 1) / (KSS_MAX_NPT * KSS_MAX_THREADS)));
   W = std::min(W, std::max(1, (int)N));
   const bool window = ctx->prof.pct_nodes_to_score < 100;  // k_schedule's window exchange: W + 1 values
@@ -5672,29 +5690,15 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
     if (!f64_exact(bc, bp, podsets[s].n_pods)) return demote(GP_SWEEP_VALUES, s, -1);
     PiRecords pi;
     // the volumes form: vol_form_admit per scenario, condition 4 on the scenario's own columns
-    const size_t Ns = (size_t)std::max(cl.n_nodes, 0);
-    std::vector<int32_t> att_max((size_t)std::max(cl.n_vol_keys, 1), 0), lim_max((size_t)std::max(cl.n_vol_keys, 1), -1);
+    std::vector<int32_t> att_max, lim_max;
     VolAdmit va;
-    if (pl.vform) {
-      for (int k = 0; k < cl.n_vol_keys; k++)
-        for (size_t n = 0; n < Ns; n++) {
-          att_max[(size_t)k] = std::max(att_max[(size_t)k], cl.vol_attached[(size_t)k * Ns + n]);
-          lim_max[(size_t)k] = std::max(lim_max[(size_t)k], cl.vol_limit[(size_t)k * Ns + n]);
-        }
-      va.n_rows = cl.n_vol_rows;
-      va.n_keys = cl.n_vol_keys;
-      va.row_key = cl.vol_row_key;
-      va.att_max = att_max.data();
-      va.lim_max = lim_max.data();
-    }
+    if (pl.vform) vol_admit_of(cl, att_max, lim_max, va);
     if (!build_spods(&podsets[s], 0, pl.spods[s], nullptr, pl.form ? &pi : nullptr, false, pl.form, pl.vform ? &va : nullptr)) {
       if (pl.vform && pi.vol_code != GP_OK) return demote(pi.vol_code, s, pi.vol_pod);  // the form's own reason
       // (no programs, no volumes: fill_spod refused a pod's preferred NodeAffinity weights)
       const int64_t lim = pl.form ? (int64_t)SWPI_NA_MAX : 0xFFFFF;
       for (int i = 0; i < podsets[s].n_pods; i++) {
-        const kss_pod& p = podsets[s].pods[i];
-        int64_t wsum = 0;
-        for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, podsets[s].terms[p.pref_off + t].weight);
+        const int64_t wsum = pref_weight_sum(&podsets[s], podsets[s].pods[i]);
         if (wsum > lim) return demote(wsum > 0xFFFFF ? GP_NA_WEIGHTS : GP_PI_NA_WEIGHTS, s, i);
       }
       return demote(GP_NA_WEIGHTS, s, -1);
@@ -5911,13 +5915,17 @@ int kss_sweep_run(kss_sweep* sw, int32_t* chosen_out, double* device_ms) {
   HIP_TRY(dev_zero(sw->arena + sw->cursor_off, 4 * (size_t)sw->n_scen, st));  // every scenario's scheduler starts at node 0
   const DevJob* jobs = reinterpret_cast<const DevJob*>(sw->arena + sw->jobs_off);
   int rc;
-  if (sw->simple)
-    rc = launch_simple(st, sw->g, sw->n_scen, jobs, sw->prof, sw->max_pods, sw->max_nodes, sw->chunk, nullptr, 0, err, nullptr,
-                       nullptr, nullptr, 0, false, nullptr, sw->max_keys, sw->st2, &sw->pev, 0, 0, false,
-                       sw->form ? reinterpret_cast<const SPort*>(sw->arena + sw->sports_off) : nullptr,
-                       sw->form ? reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off) : nullptr,
-                       sw->vform ? reinterpret_cast<const SVolLaunch*>(sw->arena + sw->vls_off) : nullptr);
-  else
+  if (sw->simple) {
+    SimpleLaunch L;
+    L.g = sw->g, L.n_jobs = sw->n_scen, L.jobs = jobs;
+    L.prof = &sw->prof, L.st2 = sw->st2, L.pev = &sw->pev;
+    L.n_pods = sw->max_pods, L.max_nodes = sw->max_nodes, L.chunk = sw->chunk;
+    L.n_keys = sw->max_keys, L.err = err;
+    if (sw->form) L.sports = reinterpret_cast<const SPort*>(sw->arena + sw->sports_off);
+    if (sw->form) L.pod_off = reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off);
+    if (sw->vform) L.vl = reinterpret_cast<const SVolLaunch*>(sw->arena + sw->vls_off);
+    rc = launch_simple(st, L);
+  } else
     rc = launch_schedule(st, sw->g, sw->n_scen, sw->need.bins_cap + (sw->prof.pct_nodes_to_score < 100 ? 1 : 0),
                          sw->need.general, sw->max_keys, jobs, sw->prof, nullptr, err);
   if (rc) return rc;
@@ -6348,20 +6356,10 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   out3[1] = -1;
   out3[2] = GP_OK;
   PiRecords pi;  // (follows the process-wide options simple_ports_images and simple_volumes)
-  // the volumes form's admission on the cluster as given (run_single reads the device's columns)
-  const size_t N = (size_t)std::max(cl->n_nodes, 0);
-  std::vector<int32_t> att_max((size_t)std::max(cl->n_vol_keys, 1), 0), lim_max((size_t)std::max(cl->n_vol_keys, 1), -1);
-  for (int k = 0; k < cl->n_vol_keys; k++)
-    for (size_t n = 0; n < N; n++) {
-      att_max[(size_t)k] = std::max(att_max[(size_t)k], cl->vol_attached[(size_t)k * N + n]);
-      lim_max[(size_t)k] = std::max(lim_max[(size_t)k], cl->vol_limit[(size_t)k * N + n]);
-    }
+  // the volumes form's admission on the cluster as given (plan_batch reads the device's columns)
+  std::vector<int32_t> att_max, lim_max;
   VolAdmit va;
-  va.n_rows = cl->n_vol_rows;
-  va.n_keys = cl->n_vol_keys;
-  va.row_key = cl->vol_row_key;
-  va.att_max = att_max.data();
-  va.lim_max = lim_max.data();
+  vol_admit_of(*cl, att_max, lim_max, va);
   if (build_spods(ps, cl->n_scalar, sp, nullptr, &pi, false, false, &va)) {
     out3[0] = 1;
     return 0;
@@ -6397,7 +6395,7 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
   for (int i = 0; i < ps->n_pods && names_pod < 0; i++)
     if (ps->pods[i].names_len >= 0) names_pod = i;
   const bool win = num_feasible_to_find(cl->n_nodes, prof->pct_nodes_to_score) < cl->n_nodes;
-  const bool spread_def = out3[0] == 2 && same_profile(*prof, default_profile_c()) && !opt(O_FOLD);
+  const bool spread_def = out3[0] == 2 && spread_window_profile_ok(*prof);
   // k_simple's volumes form (the plan above admitted the batch to it) runs the window only with the
   // option simple_volumes_window
   int vol_pod = -1;
@@ -6408,7 +6406,7 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
     out3[0] = 0;
     out3[1] = vol_pod;
     out3[2] = GP_VOL_PCT;
-  } else if (win && ((out3[0] == 2 && !spread_def) || names_pod >= 0)) {
+  } else if ((win && out3[0] == 2 && !spread_def) || window_names_block(win, names_pod >= 0)) {
     out3[1] = names_pod >= 0 ? names_pod : (ps->n_pods > 0 ? 0 : -1);
     out3[0] = 0;
     out3[2] = GP_PCT;
@@ -6445,8 +6443,7 @@ int kss_plan_service(const kss_cluster* cl, const kss_podset* ps, const kss_prof
     if (p.n_hard | p.n_soft | p.ipa_len) return refuse(GP_SVC_PROGRAMS, i);
     if (p.vol_len > 0) return refuse(GP_SVC_VOLUMES, i);
     if (!form && pod_ports_images(p)) return refuse(GP_SVC_PORTS_IMAGES, i);
-    int64_t wsum = 0;
-    for (int t = 0; t < p.pref_len; t++) wsum += std::max(0, ps->terms[p.pref_off + t].weight);
+    const int64_t wsum = pref_weight_sum(ps, p);
     if (wsum > 0xFFFFF) return refuse(GP_NA_WEIGHTS, i);
     if (form && wsum > (int64_t)SWPI_NA_MAX) return refuse(GP_SVC_PI_NA_WEIGHTS, i);
     if (names_pod < 0 && p.names_len >= 0) names_pod = i;
