@@ -501,7 +501,19 @@ const char* kss_last_error(void); /* thread-local message of the last failing ca
  * is routed as before the option existed; kss_plan_podset_ex follows it),
  * "sweep_volumes" (default 0; effective only with "sweep_ports_images" 1: a scenario sweep whose pods
  * hold volume programs is staged instead of refused -- see kss_sweep_create; a sweep without such a
- * pod is staged and launched as with 0; kss_plan_sweep follows it).  Read when a context is created (shards, xcd, xcd_shards,
+ * pod is staged and launched as with 0; kss_plan_sweep follows it),
+ * "spread_volumes" (default 0; effective only with "spread_ports_images" 1, independent of
+ * "simple_volumes": a staged, unrecorded batch WITH spread / inter-pod programs that meets the
+ * conditions of k_spread's ports-and-images form -- one part, "fold" 0, an empty nominator,
+ * preferred NodeAffinity weights summing to at most 8191 per pod -- and holds a pod with a volume
+ * program runs on k_spread's volumes form, kss_last_spread_form, instead of k_schedule, chunked
+ * launches, runtime profiles and, under k_spread's own window rules (default profile, no pod with
+ * a PreFilterResult node list), percentageOfNodesToScore below 100 included -- provided no pod has
+ * a WaitForFirstConsumer claim, the cluster has at most 64 volume rows and 8 attach-limit keys,
+ * every shared KSS_VOL_LIMIT entry names its row's key, and per key the largest attached count plus
+ * everything the batch can add, and every limit, stay below 65535; the statistics fold, split
+ * grids, the node axis, sweeps and the service grid do not take such batches; a batch without a
+ * volume program is routed and launched as with 0; kss_plan_podset follows it).  Read when a context is created (shards, xcd, xcd_shards,
  * no_simple, no_spread, threads, nodes_per_shard, axis_*) or at each launch (the rest).
  * KSS_E_NOTFOUND for an unknown name.  kss_set_stamps_file: per-phase timestamps of every launch
  * of contexts created afterwards are appended to `path` (NULL: off). */
@@ -900,6 +912,15 @@ int kss_last_geometry(kss_ctx* ctx, int32_t* out3);
  * adds 8 bytes per node slot, the UsedPorts column, and one uint4 to each of the three staged
  * records; a batch without a host-port / image pod asks the same with the option on and off. */
 int kss_last_spread_lds(kss_ctx* ctx, int64_t* bytes);
+/* The form of k_spread the last run took: out2[0] = 0 plain, 1 the ports-and-images form (option
+ * "spread_ports_images"), 2 its volumes form (option "spread_volumes": the pods' volume records in
+ * their staged records, and per node slot 40 more bytes of LDS -- a used-rows word, two words of
+ * packed attach counters, two of packed limits -- whatever the cluster's key count); out2[1] = the
+ * loop kernel's dynamic LDS bytes per workgroup (kss_last_spread_lds).  Both 0 when the last run was
+ * not on k_spread.  kss_last_kernel stays 2; after a run of the volumes form kss_last_timing counts
+ * three launches per chunk (k_static_pi, k_static_vol, k_spread_vol) and two for the write-back of
+ * vol_attached and vol_count. */
+int kss_last_spread_form(kss_ctx* ctx, int32_t* out2);
 /* XCD-local grid of the last run: out2[0] = 1 when its k_simple shards ran on one XCD (the
  * per-pod exchange in that XCD's L2: a cluster of at most CUs-per-XCD shards, one node per lane;
  * KSS_XCD=0 disables it), out2[1] = the chunks that found fewer workgroups on that XCD than shards

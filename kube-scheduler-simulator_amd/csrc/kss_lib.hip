@@ -88,7 +88,7 @@ enum KssOpt {
   O_THREADS, O_FORCE_THREADS, O_COOP_LAUNCH, O_NO_CACHE, O_STATIC_BYTES, O_STATIC_PPB, O_FOLD, O_TRACE_PATH,
   O_SVC_INLINE_SWEEP, O_SERVICE_STAMPS, O_SVC_FULL_FENCE, O_SERVICE_GENERAL, O_SVC_XCD, O_SVC_NO_STATIC,
   O_SWEEP_PIPE, O_SERVICE_NO_DIFF, O_SVC_HUGE, O_XCD_FORCE_FALLBACK, O_SPREAD_TWO_LEVEL, O_SPREAD_LB256, O_SHAPE_TABLE,
-  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_SIMPLE_VOL, O_SIMPLE_VOL_WIN, O_SWEEP_VOL, O_N
+  O_FLAT_EXCHANGE, O_SIMPLE_PI, O_TABLE_IMAGES, O_SPREAD_PI, O_SERVICE_PI, O_SWEEP_PI, O_SIMPLE_VOL, O_SIMPLE_VOL_WIN, O_SWEEP_VOL, O_SPREAD_VOL, O_N
 };
 struct OptDef {
   const char* name;
@@ -134,6 +134,7 @@ const OptDef kOptDefs[O_N] = {
     {"simple_volumes", "KSS_SIMPLE_VOLUMES", 0},  // k_simple's volumes form for pods with volume programs (effective only with simple_ports_images 1)
     {"simple_volumes_window", "KSS_SIMPLE_VOLUMES_WINDOW", 0},  // that form under the percentageOfNodesToScore window (effective only with the two above)
     {"sweep_volumes", "KSS_SWEEP_VOLUMES", 0},  // scenario sweeps admit pods with volume programs: k_simple_vol_sweep or k_schedule (effective only with sweep_ports_images 1)
+    {"spread_volumes", "KSS_SPREAD_VOLUMES", 0},  // k_spread's volumes form for batches with programs and volume pods, window included (effective only with spread_ports_images 1; independent of simple_volumes)
 };
 std::atomic<long long> g_opt[O_N];
 std::once_flag g_opt_once;
@@ -515,6 +516,11 @@ static void launch_static_vol(hipStream_t st, const DevJob* jobs, const kss_prof
                               const SVolLaunch* vl, int n_jobs = 1);
 static void launch_vol_writeback(hipStream_t st, const DevJob* jobs, int n_nodes, int n_pods, const SVolLaunch* vl);
 static int vol_pack_state(kss_ctx* ctx, bool& fits);
+// ... and the volumes form of k_spread (option spread_volumes), behind those: k_spread_vol<DEF, LB, WIN> and the
+// final check of its last write-back, which sums the mutable volume columns too
+static const void* spread_vol_fn(bool def, bool lb, bool win);
+__global__ void k_handoff_final_vol(const DevJob* __restrict__ jobs, int W, int w_off, int n_res, HandoffCheck hc, int* err,
+                                    const SVolLaunch* vl);
 // The form's launch block on the device (kss_ctx::vol_state_buf): SVolLaunch, the maxima k_vol_pack
 // reports, then the used / attached / limit columns of N nodes.
 struct VolStateLayout {
@@ -921,6 +927,7 @@ struct GpodNeeds {
   int gs() const { return (xw + 15) / 16 * 16; }  // granule stride per shard: whole 128-byte lines
   int fail_code = 0, fail_pod = -1;  // why / where build_gpods refused (GP_*)
   bool pi = false;        // records of the ports-and-images form (option spread_ports_images): an SPort ends each
+  bool vol = false;       // ... of its volumes form (option spread_volumes): the pod's SVol ahead of that SPort
 };
 
 // Per-batch LDS / exchange sizing: the host restatement of make_plan's bin counts.
@@ -1050,6 +1057,10 @@ struct kss_ctx {
   std::vector<uint4> gpod_host;  // records, gneed.gq uint4 each
   bool gpod_ok = false;
   bool gpod_pi = false;  // ... of the ports-and-images form (option spread_ports_images; GpodNeeds::pi)
+  // ... of its volumes form (option spread_volumes; GpodNeeds::vol): svol_host / svol_buf, spod_vol_add and
+  // vol_state_buf then serve k_spread as they serve k_simple_vol (a staged batch is of one kernel's form)
+  bool gpod_vol = false;
+  int last_spread_form[2] = {0, 0};  // the last run on k_spread: 0 plain, 1 ports-and-images, 2 volumes; its LDS bytes
   GpodNeeds gneed;
   bool no_spread = false;     // KSS_NO_SPREAD: batches with programs always take k_schedule
   double count_bound0 = 0;    // max(Σ class_count, Σ term_count) of the loaded snapshot
@@ -1587,8 +1598,20 @@ enum {
   GP_VOL_ROW_KEY,
   GP_VOL_PCT,
   GP_VOL_FIELD0,  // + the key, 0 .. SV_KEYS - 1
-  GP_NCODES = GP_VOL_FIELD0 + SV_KEYS
+  // the same limits as k_spread's volumes form states them (spread_vol_code)
+  GP_SPREAD_VOL_WFFC = GP_VOL_FIELD0 + SV_KEYS,
+  GP_SPREAD_VOL_ROWS,
+  GP_SPREAD_VOL_KEYS,
+  GP_SPREAD_VOL_ROW_KEY,
+  GP_SPREAD_VOL_FIELD0,  // + the key
+  GP_NCODES = GP_SPREAD_VOL_FIELD0 + SV_KEYS
 };
+// vol_form_admit's refusal as k_spread's volumes form reports it
+inline int spread_vol_code(int c) {
+  if (c >= GP_VOL_FIELD0 && c < GP_VOL_FIELD0 + SV_KEYS) return GP_SPREAD_VOL_FIELD0 + (c - GP_VOL_FIELD0);
+  return c == GP_VOL_WFFC ? GP_SPREAD_VOL_WFFC : c == GP_VOL_ROWS ? GP_SPREAD_VOL_ROWS : c == GP_VOL_KEYS ? GP_SPREAD_VOL_KEYS
+                                                                                                         : GP_SPREAD_VOL_ROW_KEY;
+}
 const char* const kGpReason[GP_NCODES] = {
     "eligible",
     "preferred NodeAffinity weights exceed the static word",
@@ -1638,6 +1661,21 @@ const char* const kGpReason[GP_NCODES] = {
     KSS_VOL_FIELD_REASON(0), KSS_VOL_FIELD_REASON(1), KSS_VOL_FIELD_REASON(2), KSS_VOL_FIELD_REASON(3),
     KSS_VOL_FIELD_REASON(4), KSS_VOL_FIELD_REASON(5), KSS_VOL_FIELD_REASON(6), KSS_VOL_FIELD_REASON(7),
 #undef KSS_VOL_FIELD_REASON
+    "a WaitForFirstConsumer claim in a batch with programs (the binder's assume cache is global state that crosses "
+    "shards): k_spread's volumes form does not take it, k_schedule only",
+    "more than 64 volume rows in a batch with programs (k_spread's volumes form keeps a node's used rows in one 64-bit "
+    "word): k_schedule only",
+    "more than 8 attach-limit keys in a batch with programs (k_spread's volumes form packs 8 counters per node): "
+    "k_schedule only",
+    "a volume program k_spread's volumes form cannot restate (a shared volume listed under another limit key than its "
+    "row's, or one key's entries in two runs): k_schedule only",
+#define KSS_SPREAD_VOL_FIELD_REASON(k)                                                                               \
+  "attach-limit key " #k ": the attached count the batch can reach, or a node's limit, exceeds 65534 (k_spread's " \
+  "volumes form packs 16-bit counters): k_schedule only"
+    KSS_SPREAD_VOL_FIELD_REASON(0), KSS_SPREAD_VOL_FIELD_REASON(1), KSS_SPREAD_VOL_FIELD_REASON(2),
+    KSS_SPREAD_VOL_FIELD_REASON(3), KSS_SPREAD_VOL_FIELD_REASON(4), KSS_SPREAD_VOL_FIELD_REASON(5),
+    KSS_SPREAD_VOL_FIELD_REASON(6), KSS_SPREAD_VOL_FIELD_REASON(7),
+#undef KSS_SPREAD_VOL_FIELD_REASON
 };
 static_assert(SV_KEYS == 8, "one reason text per key");
 
@@ -1747,15 +1785,34 @@ bool gfail(GpodNeeds& need, int code, int pod) {
 // rows: need.pi): such pods are admitted, every record is of that form (fill_spod's 13-bit limit
 // on raw NodeAffinity) and ends in the pod's SPort, one uint4 behind the longest reference list.
 // A batch without such a pod is built exactly as with the option off.
+// The volumes form (option spread_volumes with spread_ports_images, a variant of that form; va / vr: the
+// callers that can route a batch to it -- kss_plan_podset, stage_spods): a batch that holds a pod with a
+// volume program is put to vol_form_admit, the one admission k_simple's volumes form uses.  Admitted
+// (need.vol; vr: the pods' SVol records and per-key adds), every record is of the ports-and-images form and
+// carries the pod's SVol in the four uint4 ahead of its SPort; refused, the batch keeps k_schedule with the
+// limit's own reason.  Without the option, va or such a pod the batch is built exactly as before.
 bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_t* key_card, const uint32_t* key_flags,
-                 const int32_t* key_empty, std::vector<uint4>& words, GpodNeeds& need) {
+                 const int32_t* key_empty, std::vector<uint4>& words, GpodNeeds& need, const VolAdmit* va = nullptr,
+                 PiRecords* vr = nullptr) {
   std::vector<GPod> out((size_t)std::max(ps->n_pods, 1), GPod{});
   std::vector<std::vector<uint32_t>> refs_of((size_t)std::max(ps->n_pods, 1));
   need = GpodNeeds{};
   bool pi = false;
   if (opt(O_SPREAD_PI) && !opt(O_FOLD))  // (no PI instantiation of the statistics fold)
     for (int i = 0; i < ps->n_pods; i++) pi |= pod_ports_images(ps->pods[i]);
+  bool vol = false;
+  if (opt(O_SPREAD_PI) && !opt(O_FOLD) && opt(O_SPREAD_VOL) && va && vr) {
+    int first = -1;
+    for (int i = 0; i < ps->n_pods && first < 0; i++)
+      if (ps->pods[i].vol_len > 0) first = i;
+    if (first >= 0) {
+      *vr = PiRecords{};
+      if (!vol_form_admit(ps, *va, *vr)) return gfail(need, spread_vol_code(vr->vol_code), vr->vol_pod);
+      pi = vol = true;
+    }
+  }
   need.pi = pi;
+  need.vol = vol;
   std::vector<int32_t> local;  // count row -> resident index (-1 none)
   auto res_of = [&](int rowid) -> int {
     if ((size_t)rowid >= local.size()) local.resize((size_t)rowid + 1, -1);
@@ -1769,8 +1826,8 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     const kss_pod& p = ps->pods[i];
     GPod& g = out[(size_t)i];
     std::vector<uint32_t>& R = refs_of[(size_t)i];
-    if ((!pi && pod_ports_images(p)) || p.vol_len > 0) return gfail(need, GP_PORTS_IMAGES, i);
-    if (!fill_spod(ps, p, n_scalar, g.dyn, pi)) {
+    if ((!pi && pod_ports_images(p)) || (!vol && p.vol_len > 0)) return gfail(need, GP_PORTS_IMAGES, i);
+    if (!fill_spod(ps, p, n_scalar, g.dyn, pi, vol)) {
       const int64_t wsum = pref_weight_sum(ps, p);  // the form's own limit, or weights no static word holds
       return gfail(need, pi && wsum <= 0xFFFFF ? GP_SPREAD_PI_NA_WEIGHTS : GP_NA_WEIGHTS, i);
     }
@@ -1991,7 +2048,8 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     }
   }
   // records: header + references, one stride of gq uint4 each
-  const size_t gq = (sizeof(GPod) + 4 * rmax + 15) / 16 + (pi ? 1 : 0);  // pi: the SPort, the record's last uint4
+  // pi: the SPort, the record's last uint4; vol: the SVol, the four ahead of it
+  const size_t gq = (sizeof(GPod) + 4 * rmax + 15) / 16 + (pi ? 1 : 0) + (vol ? sizeof(SVol) / 16 : 0);
   if (gq > (size_t)G_QMAX) return gfail(need, GP_RECORD, rmax_pod);
   need.gq = (int)gq;
   words.assign(gq * out.size(), uint4{0, 0, 0, 0});
@@ -2002,6 +2060,7 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     if (pi && i < (size_t)ps->n_pods) {
       const SPort sp{ps->pods[i].port_conflict, ps->pods[i].port_add};
       std::memcpy(rec + 16 * (gq - 1), &sp, sizeof(SPort));
+      if (vol) std::memcpy(rec + 16 * (gq - 1) - sizeof(SVol), &vr->vols[i], sizeof(SVol));
     }
   }
   return true;
@@ -3573,7 +3632,7 @@ static int spread_cap(const Geometry& g, size_t N) {
 }
 
 static size_t spread_lds(const Geometry& g, const GpodNeeds& q, int n_keys, int n_res, size_t N, int nsc) {
-  return spread_lds_bytes(spread_cap(g, N), q.bins_cap, n_keys, n_res, q.gq, nsc, opt(O_FOLD) != 0, q.pi);
+  return spread_lds_bytes(spread_cap(g, N), q.bins_cap, n_keys, n_res, q.gq, nsc, opt(O_FOLD) != 0, q.pi, q.vol);
 }
 
 static bool spread_fits(const Geometry& g, const GpodNeeds& q, int n_keys, int n_res, size_t N, int nsc) {
@@ -3587,17 +3646,20 @@ static bool spread_fits(const Geometry& g, const GpodNeeds& q, int n_keys, int n
 // each shard's last epilogue (int), the diagnosis list, the shadow copy of the node state.
 struct HandoffLayout {
   size_t o_xcc, o_diag, o_shadow, words;
-  HandoffLayout(int W, int n_res, int N, int nsc, bool pi = false) {  // pi: the UsedPorts column behind the scalar columns
+  // pi: the UsedPorts column behind the scalar columns; vol: used and the two att words behind that (lim is read-only)
+  HandoffLayout(int W, int n_res, int N, int nsc, bool pi = false, bool vol = false) {
     o_xcc = 2 * (size_t)W;
     o_diag = o_xcc + ((size_t)W + 1) / 2;
     o_shadow = (o_diag + 1 + (size_t)HANDOFF_DIAG * HANDOFF_DIAG_W + 15) / 16 * 16;
-    words = o_shadow + (6 + (size_t)std::max(n_res, 0) + (size_t)std::max(nsc, 0) + (pi ? 1 : 0)) * (size_t)std::max(N, 1);
+    words = o_shadow + (6 + (size_t)std::max(n_res, 0) + (size_t)std::max(nsc, 0) + (pi ? 1 : 0) + (vol ? 3 : 0)) *
+                           (size_t)std::max(N, 1);
   }
 };
 
 // k_spread's family; the window (default profile, no fold) and the ports-and-images form (no fold; defined at
 // the end of this file) have their own instantiations.  launch_spread refuses the combinations that have none.
-static const void* spread_fn(bool def, bool fold, bool lb, bool win, bool pi) {
+static const void* spread_fn(bool def, bool fold, bool lb, bool win, bool pi, bool vol) {
+  if (vol) return spread_vol_fn(def, lb, win);
   const void* fn = lb ? (def ? (fold ? (const void*)k_spread<true, true, 256, false> : (const void*)k_spread<true, false, 256, false>)
                              : (fold ? (const void*)k_spread<false, true, 256, false> : (const void*)k_spread<false, false, 256, false>))
                       : (def ? (fold ? (const void*)k_spread<true, true, KSS_MAX_THREADS, false>
@@ -3614,6 +3676,10 @@ struct SpreadLaunch : LoopLaunch {
   const GpodNeeds* q = nullptr;  // the batch's needs (with the window's count area when k_find > 0)
   int n_res = 0;                 // its resident count rows
   unsigned long long *ck = nullptr, *ck_seq = nullptr;  // the checked hand-off's buffer (HandoffLayout), its tag counter
+  // the volumes form (q->vol; vl: the launch block on the device, vol_pack_state): k_static_pi + k_static_vol +
+  // k_spread_vol per chunk, the mutable columns carried through the checked hand-off, then the packed attached
+  // counts back into vol_attached and the pods' own rows into vol_count (k_vol_unpack, k_vol_counts)
+  const SVolLaunch* vl = nullptr;
 };
 
 // k_static + k_spread over pods [0, n_pods) of one job, `chunk` pods at a time (node state
@@ -3639,10 +3705,11 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
   if (L.k_find > 0 && (!def || fold)) return fail(KSS_E_INVAL, "k_spread window: default profile, no statistics fold");
   // the ports-and-images form (build_gpods need.pi; plan_batch checked: one part, no fold): k_static_pi's words
   if (q.pi && (fold || L.split)) return fail(KSS_E_INVAL, "k_spread ports-and-images form: one part, no statistics fold");
+  if (q.vol && (!q.pi || !L.vl)) return fail(KSS_E_INVAL, "k_spread volumes form: the ports-and-images form with its launch block");
   XPeers X = L.split ? L.split->X : XPeers{};
   const bool sp_grid = X.n > 1;
   bool xcd = L.xcd && !sp_grid && L.gran && g.W > 1;
-  const void* fn = spread_fn(def, fold, lb, L.k_find > 0, q.pi);
+  const void* fn = spread_fn(def, fold, lb, L.k_find > 0, q.pi, q.vol);
   const dim3 grid((unsigned)(sp_grid ? X.wl : g.W));
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   // many shards on one part: the two-level selectHost exchange, its area at the end of the
@@ -3655,7 +3722,7 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
   int W = g.W, n_lo = 0, n_hi = 0;
   static_rows(g, X, L.max_nodes, n_lo, n_hi);
   // the checked node-state hand-off (HandoffCheck): tags increase over the context's life
-  const HandoffLayout hl(g.W, L.n_res, L.max_nodes, L.nsc, q.pi);
+  const HandoffLayout hl(g.W, L.n_res, L.max_nodes, L.nsc, q.pi, q.vol);
   auto handoff = [&](unsigned long long expect, unsigned long long write) {
     HandoffCheck hc{};
     if (!L.ck || !L.ck_seq) return hc;
@@ -3671,6 +3738,10 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
     const int ci = k0 / std::max(L.chunk, 1);
     launch_static(st, def, L.jobs, pr, 1, k0, k1, n_lo, n_hi, L.n_keys, 0, q.pi);
     HIP_TRY(hipGetLastError());
+    if (q.vol) {  // VolumeBinding / VolumeZone verdicts into the words just written (the policy bits stay)
+      launch_static_vol(st, L.jobs, pr, k0, k1, n_lo, n_hi, L.vl, 1);
+      HIP_TRY(hipGetLastError());
+    }
     // every chunk's tags above the previous chunk's (a line an earlier chunk left in an XCD's
     // L2 never carries a current tag), the buffer zeroed as well
     unsigned epoch0 = (unsigned)ci * chunk_span(L.chunk);
@@ -3687,15 +3758,20 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
     HandoffCheck hc = handoff(expect, L.ck && L.ck_seq ? ++*L.ck_seq : 0ull);
     void* args[] = {(void*)&L.jobs, (void*)&W,  (void*)&cap, (void*)&bins_cap, (void*)&nr,  (void*)&gq, (void*)&gs, (void*)&k0,
                     (void*)&k1,   (void*)&gc, (void*)&L.err, (void*)&sp,       (void*)&nst, (void*)&X,  (void*)&epoch0,
-                    (void*)&hc,   (void*)&L.k_find};
+                    (void*)&hc,   (void*)&L.k_find, (void*)&L.vl};  // (k_spread_vol's trailing argument; the other kernels take 17)
     if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci], st));
     if (int rc = launch_chunk(st, L, fn, grid, shmem, args, X, xcd)) return rc;
     if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci + 1], st));
   }
   if (L.ck && L.ck_seq && L.n_pods > 0) {  // the last chunk's write-back, checked (nothing repairs it)
     const HandoffCheck hc = handoff(*L.ck_seq, 0ull);
-    if (q.pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
+    if (q.vol) hipLaunchKernelGGL(k_handoff_final_vol, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err, L.vl);
+    else if (q.pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
     else hipLaunchKernelGGL(k_handoff_final, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
+    HIP_TRY(hipGetLastError());
+  }
+  if (q.vol && L.n_pods > 0) {  // vol_attached and vol_count as k_schedule would have left them
+    launch_vol_writeback(st, L.jobs, L.max_nodes, L.n_pods, L.vl);
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -3733,6 +3809,7 @@ static bool spread_window_profile_ok(const kss_profile& p) { return !opt(O_FOLD)
 struct BatchPlan {
   Geometry g;
   bool simple = false, simple_pi = false, simple_vol = false, spread = false;  // k_simple and its forms, k_spread
+  bool spread_vol = false;  // ... on its volumes form (option spread_volumes)
   bool xcd_simple = false, xcd_spread = false, tab = false, flat = false;  // XCD-local grid; shape table, flat exchange
   bool window = false, spread_win = false;  // percentageOfNodesToScore < 100; ... and k_find < N (the search can stop early)
   int k_find = 0, win_find = 0;             // numFeasibleNodesToFind (N without a window); 0 unless k_find < N
@@ -3824,10 +3901,19 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   pl.cell_total = ctx->cell_bound + (commit ? (double)n * ctx->gneed.max_mult : 0.0);
   // k_spread runs the window itself (spread_schedule WIN) for default-profile pods without a
   // PreFilterResult list, the statistics fold off (one part or a split grid)
-  const bool spread_ok = loop_ok && (!windowed || spread_window_profile_ok(ctx->prof)) && ctx->gpod_ok && need.general &&
-                         !ctx->no_spread && spread_bounds_ok(ctx->gneed, pl.count_total, pl.cell_total, (int)N) &&
-                         // the ports-and-images form: one part, no fold, and the option still on (it is process-wide)
-                         (!ctx->gpod_pi || (!split && opt(O_SPREAD_PI) && !opt(O_FOLD)));
+  bool spread_ok = loop_ok && (!windowed || spread_window_profile_ok(ctx->prof)) && ctx->gpod_ok && need.general &&
+                   !ctx->no_spread && spread_bounds_ok(ctx->gneed, pl.count_total, pl.cell_total, (int)N) &&
+                   // the ports-and-images form: one part, no fold, and the option still on (it is process-wide)
+                   (!ctx->gpod_pi || (!split && opt(O_SPREAD_PI) && !opt(O_FOLD))) &&
+                   // its volumes form: that option too (the window runs under the same option)
+                   (!ctx->gpod_vol || opt(O_SPREAD_VOL));
+  // ... and the packed fields cannot overflow (vol_form_admit's condition 4) on the columns as they are now:
+  // packed here, before the batch's first launch, as for k_simple's volumes form
+  if (spread_ok && ctx->gpod_vol) {
+    bool fits = false;
+    if (int rc = vol_pack_state(ctx, fits)) return rc;
+    spread_ok = fits;
+  }
   if (opt(O_TRACE_PATH))  // diagnosis: why a batch with programs is (not) on k_spread
     fprintf(stderr,
             "kss path: staged=%d gpod_ok=%d commit=%d record=%d general=%d scalar=%d small=%d f64=%d bounds=%d "
@@ -3887,6 +3973,7 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   // XCD-local k_spread: the shards on one XCD when they fit its CUs
   if (spread && !simple && xcd_ok) pl.xcd_spread = g.W > xcd_w ? repick(xcd_w, SPREAD_PREF_THREADS) : g.W > 1;
   pl.spread = spread, pl.xcd_simple = simple && xcd_try && g.W > 1;
+  pl.spread_vol = spread && ctx->gpod_vol;
   if (split && !pl.loop())
     return fail(KSS_E_UNSUPPORTED, spread_ok ? "split grid: a k_spread shard exceeds LDS (more shards per part)"
                                              : "split grid: the batch needs k_schedule (kss_plan_podset)");
@@ -4047,6 +4134,7 @@ static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, co
   ctx->last_shape[1] = pl.tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
   ctx->last_flat[0] = pl.flat ? 1 : 0, ctx->last_flat[1] = pl.flat ? g.W * (g.threads / 64) : 0;
   ctx->last_simple_form[0] = pl.simple_vol ? 1 : 0, ctx->last_simple_form[1] = simple ? (int)pl.lds : 0;
+  ctx->last_spread_form[0] = spread ? (pl.spread_vol ? 2 : (pl.q->pi ? 1 : 0)) : 0, ctx->last_spread_form[1] = spread ? (int)pl.lds : 0;
   if (!loop) {
     rc = launch_schedule(ctx->stream, g, 1, pl.sched_bins, pl.general, ctx->dc.n_keys, jd, ctx->prof, gran, errp, run.stamps,
                          epoch0);
@@ -4071,7 +4159,7 @@ static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, co
       S.vl = pl.simple_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
       rc = launch_simple(ctx->stream, S);
     } else {
-      const HandoffLayout hl(g.W, pl.n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi);
+      const HandoffLayout hl(g.W, pl.n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi, pl.spread_vol);
       if ((rc = ctx->ck_buf.ensure(sizeof(unsigned long long) * hl.words))) return rc;
       HIP_TRY(dev_zero((unsigned long long*)ctx->ck_buf.p + hl.o_diag, sizeof(unsigned long long), ctx->stream));
       ctx->ck_diag_off = hl.o_diag;
@@ -4079,6 +4167,7 @@ static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, co
       SpreadLaunch G{L};
       G.q = pl.q, G.n_res = pl.n_res;
       G.ck = (unsigned long long*)ctx->ck_buf.p, G.ck_seq = &ctx->ck_seq;
+      G.vl = pl.spread_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
       rc = launch_spread(ctx->stream, G);
     }
   }
@@ -4112,7 +4201,8 @@ static int finish_batch(kss_ctx* ctx, const BatchPlan& pl, const BatchLaunched& 
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->last_ms = ms;
-  ctx->last_launches = pl.loop() ? 2 * run.n_chunks : 1;
+  // (the volumes form of k_spread: k_static_pi + k_static_vol + k_spread_vol per chunk, then k_vol_unpack + k_vol_counts)
+  ctx->last_launches = pl.spread_vol ? 3 * run.n_chunks + 2 : (pl.loop() ? 2 * run.n_chunks : 1);
   ctx->last_loop_ms = pl.loop() ? 0.0 : ms;
   for (int i = 0; i < run.n_chunks; i++) {
     float t = 0;
@@ -4262,12 +4352,21 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   ctx->spod_ports = false;
   for (const SPort& q : pi.ports) ctx->spod_ports |= (q.conflict | q.add) != 0;
   ctx->sport_host.swap(pi.ports);
-  ctx->gpod_ok = ctx->gpod_pi = false;
+  ctx->gpod_ok = ctx->gpod_pi = ctx->gpod_vol = false;
   if (!ctx->spod_ok) {  // programs: the resolved records of k_spread
+    PiRecords vr;  // (its volumes form: the same admission, condition 4 at the run as above)
     ctx->gpod_ok = build_gpods(ps, ctx->dc.n_scalar, ctx->dc.n_classes, ctx->key_card_h.data(), ctx->key_flags_h.data(),
-                               ctx->key_empty_h.data(), ctx->gpod_host, ctx->gneed);
+                               ctx->key_empty_h.data(), ctx->gpod_host, ctx->gneed,
+                               (int)ctx->vol_row_key_h.size() == va.n_rows ? &va : nullptr, &vr);
     if (!ctx->gpod_ok) return 0;
     ctx->gpod_pi = ctx->gneed.pi;
+    if ((ctx->gpod_vol = ctx->gneed.vol)) {  // the pods' SVol records for k_static_vol, the per-key adds for vol_pack_state
+      ctx->svol_host.swap(vr.vols);
+      for (int k = 0; k < SV_KEYS; k++) ctx->spod_vol_add[k] = vr.vol_add[k];
+      if (int rc = ctx->svol_buf.ensure(sizeof(SVol) * ctx->svol_host.size())) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->svol_buf.p, ctx->svol_host.data(), sizeof(SVol) * ctx->svol_host.size(),
+                             hipMemcpyHostToDevice, ctx->stream));
+    }
     int rc = ctx->gpod_buf.ensure(sizeof(uint4) * ctx->gpod_host.size());
     if (rc) return rc;
     if ((rc = ctx->res_buf.ensure(sizeof(int32_t) * std::max<size_t>(ctx->gneed.res_rows.size(), 1)))) return rc;
@@ -5324,6 +5423,13 @@ int kss_last_simple_exchange(kss_ctx* ctx, int32_t* out2) {
   return 0;
 }
 
+int kss_last_spread_form(kss_ctx* ctx, int32_t* out2) {
+  if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
+  out2[0] = ctx->last_spread_form[0];
+  out2[1] = ctx->last_spread_form[1];
+  return 0;
+}
+
 int kss_last_simple_form(kss_ctx* ctx, int32_t* out2) {
   if (!ctx || !out2) return fail(KSS_E_INVAL, "bad arguments");
   out2[0] = ctx->last_simple_form[0];
@@ -6366,7 +6472,8 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   }
   std::vector<uint4> words;
   GpodNeeds need;
-  if (build_gpods(ps, cl->n_scalar, cl->n_classes, cl->key_card, cl->key_flags, cl->key_empty, words, need)) {
+  PiRecords vr;  // (k_spread's volumes form: the same admission, options spread_ports_images and spread_volumes)
+  if (build_gpods(ps, cl->n_scalar, cl->n_classes, cl->key_card, cl->key_flags, cl->key_empty, words, need, &va, &vr)) {
     out3[0] = 2;
     return 0;
   }
@@ -6798,4 +6905,49 @@ static void launch_vol_writeback(hipStream_t st, const DevJob* jobs, int n_nodes
   const uint64_t* att = (const uint64_t*)((const char*)vl + L.o_att);
   hipLaunchKernelGGL(k_vol_unpack, dim3((unsigned)(std::max(n_nodes, 1) + 255) / 256), dim3(256), 0, st, jobs, att);
   hipLaunchKernelGGL(k_vol_counts, dim3((unsigned)(std::max(n_pods, 1) + 255) / 256), dim3(256), 0, st, jobs, n_pods);
+}
+
+// ---------------------------------------------------------------------------
+// k_spread's volumes form (options spread_ports_images and spread_volumes): spread_schedule<.., PI = true,
+// VOL = true>, kss_spread.cuh.  k_spread's body with the launch block `vl` as one more trailing argument
+// (k_simple_vol's way), so k_spread's own instantiations keep their signature and code.  Six kernels: {default,
+// runtime profile} x {256, KSS_MAX_THREADS lanes} and the default profile's two window kernels; never with
+// the statistics fold.  Defined here, behind every other kernel, so those keep their places in the code object.
+// ---------------------------------------------------------------------------
+template <bool DEF, int LB, bool WIN>
+__global__ __launch_bounds__(LB) void k_spread_vol(const DevJob* __restrict__ jobs, int W, int cap, int bins_cap, int n_res,
+                                                   int gq, int gs, int k0, int k1, unsigned long long* gran, int* err,
+                                                   unsigned long long* stamps, int nst, XPeers X, unsigned epoch0,
+                                                   HandoffCheck hc, int k_find, const SVolLaunch* vl) {
+  extern __shared__ __attribute__((aligned(16))) long long smem[];
+  SpreadHdr& H = *reinterpret_cast<SpreadHdr*>(smem);
+  int xs = 0;  // as k_spread (one job, one part)
+  if (X.xcd_local && (xs = claim_xcd_shard(H, X, gran, [&] { return 2 * (size_t)W * gs; }, W, err)) < 0) return;
+  const int w = X.xcd_local ? xs : (int)blockIdx.x;
+  if (w >= W) return;
+  if (X.tl) {
+    if (threadIdx.x == 0) tl_register(H, X.tl, W, err);
+    __syncthreads();
+  }
+  const DevJob job = jobs[0];
+  constexpr kss_profile def_prof = default_profile_c();
+  if (!DEF) stage_profile(H, jobs[0].prof);
+  const kss_profile& P = DEF ? def_prof : H.prof;
+  spread_schedule<DEF, false, WIN, true, true>(job.trace, job.c, job.gpods, job.stat, job.res_rows, n_res, k0,
+                                               min(k1, job.n_pods), job.chosen, job.meta, P, W, w, cap, bins_cap, gq, gs, gran,
+                                               X, epoch0, err, stamps, nst, hc, smem, k_find, job.cursor, vl);
+}
+
+__global__ __launch_bounds__(256) void k_handoff_final_vol(const DevJob* __restrict__ jobs, int W, int w_off, int n_res,
+                                                           HandoffCheck hc, int* err, const SVolLaunch* vl) {
+  __shared__ long long scratch[4];
+  const DevJob& job = jobs[0];
+  handoff_final_check<true, true>(job.c, job.res_rows, n_res, W, w_off + (int)blockIdx.x, hc, err, scratch, vl);
+}
+
+static const void* spread_vol_fn(bool def, bool lb, bool win) {
+  if (win)  // (launch_spread refuses a window under a runtime profile before it asks)
+    return lb ? (const void*)k_spread_vol<true, 256, true> : (const void*)k_spread_vol<true, KSS_MAX_THREADS, true>;
+  if (def) return lb ? (const void*)k_spread_vol<true, 256, false> : (const void*)k_spread_vol<true, KSS_MAX_THREADS, false>;
+  return lb ? (const void*)k_spread_vol<false, 256, false> : (const void*)k_spread_vol<false, KSS_MAX_THREADS, false>;
 }

@@ -196,8 +196,11 @@ struct SpreadShard {
 // slots (pods k .. k + 2: the early statistics pass of pod k + 1 reads its words during pod k)
 // pi (k_spread<.., PI = true>, the ports-and-images form): the UsedPorts column, one uint64 per slot, behind
 // every other array (spread_schedule finds it at the byte count without it)
+// vol (k_spread_vol, the volumes form, a variant of pi): behind pused the volume columns of SVolLaunch's layout --
+// used (8 B), two packed att words and two packed lim words per slot, 40 B a slot whatever the cluster's key
+// count (one layout, the one k_vol_pack / k_vol_unpack and vol_infeasible read) -- then the keys' row masks
 __host__ __device__ inline size_t spread_lds_bytes(int cap, int bins_cap, int n_keys, int n_res, int gq, int nsc = 0,
-                                                   bool fold = false, bool pi = false) {
+                                                   bool fold = false, bool pi = false, bool vol = false) {
   const size_t C = (size_t)cap;
   const size_t nb = (size_t)bins_cap * (fold ? 2 : 1), nst = fold ? 3 : 2;
   size_t b = (sizeof(SpreadHdr) + 4 * ((size_t)G_NS + nb) + 15) / 16 * 16;
@@ -205,6 +208,7 @@ __host__ __device__ inline size_t spread_lds_bytes(int cap, int bins_cap, int n_
   b += 8 * 8 * C + 8 * 3 * C + 8 * 2 * C + 4 * 3 * C + 4 * (size_t)n_keys * C + 4 * 6 * C;
   b += 16 * (size_t)nsc * C;
   if (pi) b += 8 * C;
+  if (vol) b += 40 * C + 8 * SV_KEYS;
   return b;
 }
 
@@ -1269,9 +1273,11 @@ __device__ __forceinline__ void handoff_note(const HandoffCheck& hc, int w, int 
 // sums it, against the sum and tag its epilogue stored.  A disagreement fails the run (err = 2)
 // and counts in retries[2]; nothing is repaired, so no corrupted write-back passes silently.
 // PI: the ports-and-images form's UsedPorts column, summed behind the scalar columns.
-template <bool PI = false>
+// VOL: the volumes form's mutable columns (used, the two att words of vl) behind that.
+template <bool PI = false, bool VOL = false>
 __device__ __forceinline__ void handoff_final_check(const DevCluster& c, const int32_t* __restrict__ res_rows, int n_res,
-                                                    int W, int w, const HandoffCheck& hc, int* err, long long* scratch) {
+                                                    int W, int w, const HandoffCheck& hc, int* err, long long* scratch,
+                                                    const SVolLaunch* vl = nullptr) {
   const size_t N = (size_t)c.N;
   const int per = (c.N + W - 1) / W;
   const int lo = min(c.N, w * per), hi = min(c.N, lo + per), own = hi - lo, nsc = c.n_scalar;
@@ -1290,6 +1296,12 @@ __device__ __forceinline__ void handoff_final_check(const DevCluster& c, const i
     for (int i = 0; i < nsc; i++)
       h += handoff_mix((unsigned long long)ld_ag(&c.requested[(size_t)(3 + i) * N + n]), (6 + (size_t)n_res + i) * N + n);
     if constexpr (PI) h += handoff_mix((unsigned long long)ld_ag(&c.port_used[n]), (6 + (size_t)n_res + nsc) * N + n);
+    if constexpr (VOL) {
+      const size_t a = 7 + (size_t)n_res + nsc;
+      h += handoff_mix((unsigned long long)ld_ag(&vl->used[n]), a * N + n) +
+           handoff_mix((unsigned long long)ld_ag(&vl->att[n]), (a + 1) * N + n) +
+           handoff_mix((unsigned long long)ld_ag(&vl->att[N + n]), (a + 2) * N + n);
+    }
   }
   for (int i = threadIdx.x; i < n_res * own; i += blockDim.x) {
     const int r = i / own, s = i - r * own, row = res_rows[r];
@@ -1520,14 +1532,26 @@ __device__ __forceinline__ int32_t trace_eff(const SpreadShard& L, const GPod& q
 // The ImageLocality score travels above the Fit score in L.sfit (pi_fix: fit | il << 8).  AssumePod:
 // the winner's slot ORs port_add on lane 6 of the commit block, before the pod's closing barrier;
 // the column is read only by the next pod's filter pass.
-template <bool DEF, bool FOLD, bool WIN, bool PI = false>
+// VOL: the volumes form (option spread_volumes; a variant of PI, kss_simple.cuh SVol).  The static words
+// are k_static_vol's (verdict 5 for a bound-claim / VolumeZone failure, the policy bits kept); a pod's SVol
+// is the four uint4 ahead of its SPort (gq - 5 .. gq - 2: it rides the record's prefetch); the node state is
+// SVolLaunch's columns in LDS behind pused (used, att x2, lim x2; vl: the launch block in HBM, its columns
+// packed by k_vol_pack before the batch's first launch and unpacked after its last).  The dynamic verdict
+// (vol_infeasible) is in e.f right behind pi_fix, where the NodePorts verdict is: before the
+// PodTopologySpread / InterPodAffinity filters and every statistic of the pass.  AssumePod (vol_commit) runs
+// on lane 7 of the commit block.  Ordering: the columns are written where pused is written (the prologue,
+// ahead of its barrier; the winner's commit, ahead of the pod's closing barrier) and read where pused is
+// read (the filter pass, which that barrier precedes; the epilogue, behind its barrier), so they need no
+// barrier of their own.
+template <bool DEF, bool FOLD, bool WIN, bool PI = false, bool VOL = false>
 __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, const GPod* __restrict__ gpods,
                                                 const uint32_t* __restrict__ stat, const int32_t* __restrict__ res_rows,
                                                 int n_res, int k0, int k1, int32_t* chosen, PodMeta* meta,
                                                 const kss_profile& prof, int W, int w, int cap, int bins_cap, int gq, int gs,
                                                 unsigned long long* gran, const XPeers& X, unsigned epoch0, int* err,
                                                 unsigned long long* stamps, int nst, const HandoffCheck& hc,
-                                                long long* smem, int k_find = 0, int32_t* cursor = nullptr) {
+                                                long long* smem, int k_find = 0, int32_t* cursor = nullptr,
+                                                const SVolLaunch* vl = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
   // WIN: nextStartNodeIndex for the launch (every shard holds the same value and writes it back, each part into its own word)
   int wstart = WIN && cursor && c.N > 0 ? (int)(((long long)ld_ag(cursor) % c.N + c.N) % c.N) : 0;
@@ -1539,6 +1563,23 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       PI ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(smem) +
                                        spread_lds_bytes(cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD))
          : nullptr;
+  static_assert(!VOL || PI, "the volumes form is a variant of the ports-and-images form");
+  VolView V{};  // VOL: the columns behind pused; ring: the current pod's SVol in its record (set per pod)
+  uint64_t *vg_used = nullptr, *vg_att = nullptr;  // ... and their packed home in HBM (vol_pack_state)
+  const uint64_t* vg_lim = nullptr;
+  if constexpr (VOL) {
+    V.cap = cap;
+    V.used = pused + cap;
+    V.att = V.used + cap;
+    V.lim = V.att + 2 * (size_t)cap;
+    uint64_t* kr = V.lim + 2 * (size_t)cap;
+    V.keyrows = kr;
+    V.key_on = vl->key_on;
+    V.key_csi = vl->key_csi;
+    V.vr_on = vl->vr_on;
+    vg_used = vl->used, vg_att = vl->att, vg_lim = vl->lim;
+    if (tid < SV_KEYS) kr[tid] = vl->keyrows[tid];  // (read behind the prologue's barrier)
+  }
   // FOLD: pod j's static words in slot j % 3 (its early statistics pass reads pod k + 1's during
   // pod k) and its bins in area j & 1; otherwise slot j & 1 and one area
   auto st_slot = [](int j) { return FOLD ? j % 3 : j & 1; };
@@ -1552,7 +1593,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
   // (no HBM store on the exchange wave while the loop runs)
   unsigned long long* stl =
       stamps ? reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(smem) +
-                                                     spread_lds_bytes(cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD, PI))
+                                                     spread_lds_bytes(cap, bins_cap, c.n_keys, n_res, gq, c.n_scalar, FOLD, PI, VOL))
              : nullptr;
   if (stl)
     for (int i = tid; i < 16 * nst; i += nt) stl[i] = 0;
@@ -1571,6 +1612,10 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
     L.r32[2 * cap + s] = (int32_t)c.node_flags[n];
     for (int k = 0; k < c.n_keys; k++) L.lbl[k * cap + s] = c.label_value[(size_t)k * N + n];
     for (int i = 0; i < nsc; i++) L.sc[(size_t)i * cap + s] = c.alloc[(size_t)(3 + i) * N + n];
+    if constexpr (VOL) {  // the limits: read-only, outside the hand-off's sum
+      V.lim[s] = ld_ag(&vg_lim[n]);
+      V.lim[cap + s] = ld_ag(&vg_lim[N + n]);
+    }
     L.st[st_slot(k0) * cap + s] = ld_ag(&stat[(size_t)lo + s]);
     if (FOLD && k0 + 1 < k1) L.st[st_slot(k0 + 1) * cap + s] = ld_ag(&stat[N + (size_t)lo + s]);
   }
@@ -1607,6 +1652,17 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
         const uint64_t pu = shd ? (uint64_t)ld_ag(&hc.shadow[a * N + n]) : ld_ag(&c.port_used[n]);
         pused[s] = pu;
         h += handoff_mix((unsigned long long)pu, a * N + n);
+      }
+      if constexpr (VOL) {  // the used rows and the two packed attached words: shadow columns behind UsedPorts
+        const size_t a = 7 + (size_t)n_res + nsc;
+        const uint64_t u = shd ? (uint64_t)ld_ag(&hc.shadow[a * N + n]) : ld_ag(&vg_used[n]);
+        const uint64_t a0 = shd ? (uint64_t)ld_ag(&hc.shadow[(a + 1) * N + n]) : ld_ag(&vg_att[n]);
+        const uint64_t a1 = shd ? (uint64_t)ld_ag(&hc.shadow[(a + 2) * N + n]) : ld_ag(&vg_att[N + n]);
+        V.used[s] = u;
+        V.att[s] = a0;
+        V.att[cap + s] = a1;
+        h += handoff_mix((unsigned long long)u, a * N + n) + handoff_mix((unsigned long long)a0, (a + 1) * N + n) +
+             handoff_mix((unsigned long long)a1, (a + 2) * N + n);
       }
     }
     for (int i = tid; i < n_res * own; i += nt) {
@@ -1894,6 +1950,7 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       const SPod qd = q.dyn;  // in registers: the loop's LDS stores would make every field a reload
       uint64_t qconflict = 0;  // PI: the pod's NodePorts conflict mask (the record's last uint4)
       if constexpr (PI) qconflict = reinterpret_cast<const SPort*>(L.ring + (k % 3) * gq + gq - 1)->conflict;
+      if constexpr (VOL) V.ring = reinterpret_cast<SVol*>(L.ring + (k % 3) * gq + gq - 5);  // the pod's SVol
       for (int s = tid; s < own; s += nt) {
         const uint32_t wd = sw[s];
         DynRow r;
@@ -1910,6 +1967,9 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
         SVal e = DEF ? dyn_eval_def(qd, wd, r) : dyn_eval(prof, qd, wd, r);
         // NodePorts, the 13-bit NodeAffinity field, ImageLocality into e.fit (fit | il << 8)
         if constexpr (PI) pi_fix<DEF>(prof, e, pused[s], qconflict);
+        // VolumeRestrictions and the attach limits on the columns (the verdict's code stands for any of them:
+        // an unrecorded batch shows only that the node is infeasible)
+        if constexpr (VOL) e.f = (e.f == 0 && vol_infeasible(V, s, false, 0, 0)) ? KSS_F_VOLUME_RESTRICTIONS : e.f;
         if (nsc && e.f == 0 && ((en >> KSS_F_NODE_RESOURCES_FIT) & 1u) && scalar_short(L.sc, nsc, cap, s, q.dyn, false, q.dyn))
           e.f = KSS_F_NODE_RESOURCES_FIT;
         if (e.f == 0 && ((en >> KSS_F_POD_TOPOLOGY_SPREAD) & 1u) && q.n_hard > 0 &&
@@ -2339,6 +2399,8 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       if (tid == 5) L.r32[s] += 1;
       if constexpr (PI)
         if (tid == 6) pused[s] |= reinterpret_cast<const SPort*>(L.ring + (k % 3) * gq + gq - 1)->add;
+      if constexpr (VOL)
+        if (tid == 7) vol_commit(V, s, 0);  // AssumePod's volumes (a winner was evaluated: V.ring is this pod's SVol)
       if (tid >= 8 && tid < 8 + nsc) L.sc[(size_t)(nsc + tid - 8) * cap + s] += pk.sc_req[tid - 8];
       if (tid == 32)
         for (int i = 0; i < q.n_cmt; i++)
@@ -2404,6 +2466,17 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       st_ag(&c.port_used[n], pused[s]);
       if (hc.shadow) st_ag(&hc.shadow[(6 + (size_t)n_res + nsc) * N + n], (long long)pused[s]);
     }
+    if constexpr (VOL) {  // the mutable volume columns back to their packed home (k_vol_unpack reads att after the last chunk)
+      const size_t a = 7 + (size_t)n_res + nsc;
+      st_ag(&vg_used[n], V.used[s]);
+      st_ag(&vg_att[n], V.att[s]);
+      st_ag(&vg_att[N + n], V.att[cap + s]);
+      if (hc.shadow) {
+        st_ag(&hc.shadow[a * N + n], (long long)V.used[s]);
+        st_ag(&hc.shadow[(a + 1) * N + n], (long long)V.att[s]);
+        st_ag(&hc.shadow[(a + 2) * N + n], (long long)V.att[cap + s]);
+      }
+    }
   }
   unsigned long long h = 0;
   if (hc.sum)
@@ -2417,6 +2490,11 @@ __device__ __forceinline__ void spread_schedule(const GTrace& tr, DevCluster c, 
       for (int i = 0; i < nsc; i++)
         h += handoff_mix((unsigned long long)L.sc[(size_t)(nsc + i) * cap + s], (6 + (size_t)n_res + i) * N + n);
       if constexpr (PI) h += handoff_mix((unsigned long long)pused[s], (6 + (size_t)n_res + nsc) * N + n);
+      if constexpr (VOL) {
+        const size_t a = 7 + (size_t)n_res + nsc;
+        h += handoff_mix((unsigned long long)V.used[s], a * N + n) + handoff_mix((unsigned long long)V.att[s], (a + 1) * N + n) +
+             handoff_mix((unsigned long long)V.att[cap + s], (a + 2) * N + n);
+      }
     }
   for (int i = tid; i < n_res * own; i += nt) {
     const int r = i / own, s = i - r * own, row = res_rows[r];

@@ -83,6 +83,7 @@ SIGNATURES = [
     ("kss_last_geometry", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_kernel", C.c_int, [C.c_void_p]),
     ("kss_last_spread_lds", C.c_int, [C.c_void_p, P(C.c_int64)]),
+    ("kss_last_spread_form", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_xcd_local", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_shape_table", C.c_int, [C.c_void_p, P(C.c_int32)]),
     ("kss_last_simple_exchange", C.c_int, [C.c_void_p, P(C.c_int32)]),
@@ -689,6 +690,14 @@ class Context:
         v = C.c_int64(0)
         check(lib().kss_last_spread_lds(self.h, C.byref(v)))
         return v.value
+
+    def last_spread_form(self) -> Tuple[int, int]:
+        """(form, lds_bytes) of the last run (kss_last_spread_form): form 0 plain k_spread, 1 its
+        ports-and-images form (option spread_ports_images), 2 its volumes form (option spread_volumes);
+        lds_bytes the loop kernel's dynamic LDS per workgroup.  (0, 0): the last run was not on k_spread."""
+        out = (C.c_int32 * 2)()
+        check(lib().kss_last_spread_form(self.h, out))
+        return (out[0], out[1])
 
     def last_xcd_local(self) -> Dict[str, int]:
         """{used, fallbacks} of the last run's XCD-local k_simple grid (kss_last_xcd_local)."""
