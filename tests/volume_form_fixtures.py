@@ -45,7 +45,9 @@ def reach(cc, cp, ch_o, res, prof=None):
     VolumeRestrictions, pods with a node failing a limit plugin, pods with a node failing VolumeBinding /
     VolumeZone, and H1 pairs -- pod k+1 fails a dynamic volume filter on the node pod k took, and would
     not on that node's state before pod k's commit.  Asserts on the way that the replayed state decides
-    every recorded dynamic verdict (default profile only) and ends in the oracle's final columns."""
+    every recorded dynamic verdict (default profile only) and ends in the oracle's final columns.
+    Also returned, with the limit key that decides them (the first failing key in filter order):
+    h1_events [(pod k+1, node, key)] and limit_failures [(pod, node, key)]."""
     cs = cc.as_struct()
     N, R, K = cc.n_nodes, cs.n_vol_rows, cs.n_vol_keys
     A = cc.arrays
@@ -59,13 +61,15 @@ def reach(cc, cp, ch_o, res, prof=None):
     enabled = (prof or abi.default_profile()).filter_enabled
     exact = prof is None
     vr = lm = stc = h1 = 0
+    h1_events, limit_failures = [], []
     prev = None
     for j in range(cp.n):
         conflict, shared, own, keys, pnew, padd = pod_masks(cc, cp, j)
 
-        def dyn_fail(u, a, n):
+        def dyn_key(u, a, n):
+            """The deciding limit key on node n's state (u, a), -1 for VolumeRestrictions, None: passes."""
             if (enabled >> abi.KSS_F_VOLUME_RESTRICTIONS) & 1 and u & conflict:
-                return True
+                return -1
             for k in range(K):
                 if not (keys >> k) & 1 or lim[n][k] < 0 or not (enabled >> plug[k]) & 1:
                     continue
@@ -73,8 +77,11 @@ def reach(cc, cp, ch_o, res, prof=None):
                 if plug[k] == abi.KSS_F_NODE_VOLUME_LIMITS and new == 0:
                     continue
                 if a[k] + new > lim[n][k]:
-                    return True
-            return False
+                    return k
+            return None
+
+        def dyn_fail(u, a, n):
+            return dyn_key(u, a, n) is not None
 
         if int(cp.pods[j]["prefilter_status"]) == 0:
             fp = res.fail_plugin[j][:N]
@@ -87,10 +94,15 @@ def reach(cc, cp, ch_o, res, prof=None):
                     if f == abi.KSS_F_NOT_EVALUATED or 0 < f < abi.KSS_F_VOLUME_RESTRICTIONS:
                         continue  # an earlier filter decided the node
                     assert dyn_fail(used[n], att[n], n) == (f in DYNAMIC), (j, n, f)
+                    if f in LIMITS:
+                        k = dyn_key(used[n], att[n], n)
+                        assert k >= 0 and plug[k] == f, (j, n, f, k)
+                        limit_failures.append((j, n, k))
             if prev is not None:
                 x, u0, a0 = prev
                 if int(fp[x]) in DYNAMIC and not dyn_fail(u0, a0, x):
                     h1 += 1
+                    h1_events.append((j, x, dyn_key(used[x], att[x], x)))
         prev = None
         x = int(ch_o[j])
         if x >= 0:
@@ -101,7 +113,8 @@ def reach(cc, cp, ch_o, res, prof=None):
             used[x] |= own
             for r in range(R):
                 cnt[r][x] += (own >> r) & 1
-    return dict(restrictions=vr, limits=lm, static=stc, h1=h1, used=used, att=att, cnt=cnt)
+    return dict(restrictions=vr, limits=lm, static=stc, h1=h1, used=used, att=att, cnt=cnt, h1_events=h1_events,
+                limit_failures=limit_failures)
 
 
 def private_ebs(n_nodes=6, n_pods=16, limit=2):
