@@ -515,7 +515,6 @@ static const void* simple_vol_sweep_fn(bool def);
 static void launch_static_vol(hipStream_t st, const DevJob* jobs, const kss_profile& pr, int k0, int k1, int n_lo, int n_hi,
                               const SVolLaunch* vl, int n_jobs = 1);
 static void launch_vol_writeback(hipStream_t st, const DevJob* jobs, int n_nodes, int n_pods, const SVolLaunch* vl);
-static int vol_pack_state(kss_ctx* ctx, bool& fits);
 // ... and the volumes form of k_spread (option spread_volumes), behind those: k_spread_vol<DEF, LB, WIN> and the
 // final check of its last write-back, which sums the mutable volume columns too
 static const void* spread_vol_fn(bool def, bool lb, bool win);
@@ -912,6 +911,13 @@ struct F64Bounds {
   bool neg = false;
 };
 
+// The form of a loop kernel and of the records it reads: plain, ports-and-images (NodePorts /
+// ImageLocality pods; k_static_pi's words), or that form's volumes variant (pods with volume
+// programs as well).  The order says it: the volumes form is a ports-and-images form.
+enum Form { FORM_PLAIN = 0, FORM_PI = 1, FORM_VOL = 2 };  // (the values are what the *_form calls report)
+inline bool form_pi(Form f) { return f >= FORM_PI; }
+inline bool form_vol(Form f) { return f == FORM_VOL; }
+
 // What the staged batch asks of k_spread (the host side of the GPod plans).
 struct GpodNeeds {
   int bins_cap = 0;       // max histogram + presence bins of a pod
@@ -926,8 +932,7 @@ struct GpodNeeds {
   int soft_xw = 0;        // max soft presence bins of a pod (its own E2)
   int gs() const { return (xw + 15) / 16 * 16; }  // granule stride per shard: whole 128-byte lines
   int fail_code = 0, fail_pod = -1;  // why / where build_gpods refused (GP_*)
-  bool pi = false;        // records of the ports-and-images form (option spread_ports_images): an SPort ends each
-  bool vol = false;       // ... of its volumes form (option spread_volumes): the pod's SVol ahead of that SPort
+  Form form = FORM_PLAIN;  // the records': ports-and-images (option spread_ports_images), an SPort ends each; volumes (spread_volumes), the pod's SVol ahead of it
 };
 
 // Per-batch LDS / exchange sizing: the host restatement of make_plan's bin counts.
@@ -1034,21 +1039,19 @@ struct kss_ctx {
   DevBuf spod_buf, stat_buf;
   std::vector<SPod> spod_host;
   bool spod_ok = false;
-  // the ports-and-images form (option simple_ports_images): the staged batch holds a NodePorts /
-  // ImageLocality pod and k_simple_pi takes it; the pods' port masks beside their records
-  bool spod_pi = false;
+  // the records' form (simple_form, at the stage; FORM_PLAIN while spod_ok is false).  Ports-and-images (option
+  // simple_ports_images): some pod has host ports or images and k_simple_pi takes the batch; the pods' port masks
+  Form spod_form = FORM_PLAIN;
   bool spod_ports = false;  // ... and some pod of it holds a host port (no shape table: UsedPorts is loop state)
   DevBuf sport_buf;
   std::vector<SPort> sport_host;
-  // its volumes form (option simple_volumes): the staged batch holds a pod with a volume program
+  // Its volumes form (option simple_volumes): the staged batch holds a pod with a volume program
   // and vol_form_admit took it (k_simple_vol, one part; the percentageOfNodesToScore window only
-  // with the option simple_volumes_window); the pods' SVol records, what
-  // their commits can add per limit key (condition 4 is checked at run time against the device's
-  // columns), and the launch's block: SVolLaunch, the packed node-state columns, the maxima
-  bool spod_vol = false;
+  // with the option simple_volumes_window); the pods' SVol records, what their commits can add per limit key (condition
+  // 4 is checked at run time against the device's columns), and the launch's block: SVolLaunch, the packed columns, the maxima
   DevBuf svol_buf, vol_state_buf;
   std::vector<SVol> svol_host;
-  uint64_t spod_vol_add[SV_KEYS] = {};
+  uint64_t staged_vol_add[SV_KEYS] = {};
   std::vector<int32_t> vol_row_key_h, vol_key_plugin_h;  // host copies (load)
   int last_simple_form[2] = {0, 0};  // the last run: the volumes form used, the loop kernel's LDS bytes
   bool staged_names = false;  // some staged pod has a NodeAffinity PreFilterResult node list
@@ -1056,10 +1059,10 @@ struct kss_ctx {
   DevBuf gpod_buf;
   std::vector<uint4> gpod_host;  // records, gneed.gq uint4 each
   bool gpod_ok = false;
-  bool gpod_pi = false;  // ... of the ports-and-images form (option spread_ports_images; GpodNeeds::pi)
-  // ... of its volumes form (option spread_volumes; GpodNeeds::vol): svol_host / svol_buf, spod_vol_add and
-  // vol_state_buf then serve k_spread as they serve k_simple_vol (a staged batch is of one kernel's form)
-  bool gpod_vol = false;
+  // ... and their form (GpodNeeds::form; FORM_PLAIN while gpod_ok is false).  In the volumes form (option
+  // spread_volumes) svol_host / svol_buf, staged_vol_add and vol_state_buf serve k_spread as they serve
+  // k_simple_vol (a staged batch is of one kernel's form)
+  Form gpod_form = FORM_PLAIN;
   int last_spread_form[2] = {0, 0};  // the last run on k_spread: 0 plain, 1 ports-and-images, 2 volumes; its LDS bytes
   GpodNeeds gneed;
   bool no_spread = false;     // KSS_NO_SPREAD: batches with programs always take k_schedule
@@ -1414,13 +1417,32 @@ inline int64_t pref_weight_sum(const kss_podset* ps, const kss_pod& p) {
   return wsum;
 }
 
-// Compact record of one pod (kss_simple.cuh SPod); false when the preferred NodeAffinity
-// weights do not fit the static word's 20 bits.  pi: a record of the ports-and-images form, which
-// admits NodePorts / ImageLocality pods and whose static word holds 13 bits of NodeAffinity.
-// vol: ... of its volumes form (option simple_volumes; the caller ran vol_form_admit), which admits volume programs.
-bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, bool pi = false, bool vol = false) {
-  if ((!pi && pod_ports_images(p)) || (!vol && p.vol_len > 0)) return false;  // NodePorts / ImageLocality / volumes: k_schedule
-  if (pref_weight_sum(ps, p) > (pi ? (int64_t)SWPI_NA_MAX : 0xFFFFF)) return false;  // static word: 20 (13) bits of raw NodeAffinity
+// The raw-NodeAffinity limit of a form's static word: 20 bits, 13 in the ports-and-images forms.
+inline int64_t na_limit(Form f) { return form_pi(f) ? (int64_t)SWPI_NA_MAX : 0xFFFFF; }
+
+// Why a pod does not fit records of form f: the first limit it hits in this order (0: it fits).
+// Each caller maps the answer to its own GP_* code, through a table of POD_N entries.
+enum PodMisfit {
+  POD_FITS = 0,
+  POD_VOLUMES,       // a volume program, and f is not the volumes form
+  POD_PORTS_IMAGES,  // host ports or node-cached images, and f is the plain form
+  POD_NA_WORD,       // preferred NodeAffinity weights no form's static word holds
+  POD_NA_FORM,       // ... that the plain word would hold and f's narrower field does not
+  POD_N
+};
+static_assert(POD_VOLUMES == 1 && POD_PORTS_IMAGES == 2 && POD_NA_WORD == 3 && POD_NA_FORM == 4 && POD_N == 5, "the tables' order");
+inline PodMisfit pod_misfit(const kss_podset* ps, const kss_pod& p, Form f) {
+  if (!form_vol(f) && p.vol_len > 0) return POD_VOLUMES;
+  if (!form_pi(f) && pod_ports_images(p)) return POD_PORTS_IMAGES;
+  const int64_t wsum = pref_weight_sum(ps, p);
+  if (wsum > na_limit(FORM_PLAIN)) return POD_NA_WORD;
+  return wsum > na_limit(f) ? POD_NA_FORM : POD_FITS;
+}
+
+// Compact record of one pod (kss_simple.cuh SPod) for records of form f (the volumes form: the
+// caller ran vol_form_admit); q is untouched and the answer says why when the pod does not fit them.
+PodMisfit fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, Form f) {
+  if (const PodMisfit m = pod_misfit(ps, p, f)) return m;  // another kernel's pod
   q = SPod{};
   bool all_zero = true;
   for (int r = 0; r < 3 + n_scalar; r++) all_zero &= p.fit_request[r] == 0;
@@ -1441,26 +1463,19 @@ bool fill_spod(const kss_podset* ps, const kss_pod& p, int n_scalar, SPod& q, bo
   q.cls = p.cls;
   q.own_off = p.own_terms_off;
   q.own_len = p.own_terms_len;
-  return true;
+  return POD_FITS;
 }
 
-// Compact records of every pod of a (validated) podset for k_simple; false when some pod
-// needs another kernel (spread / inter-pod-affinity programs, or fill_spod refuses it).
-// n_shapes (optional): the batch's resource shapes (SPod::shape, SPod::shape_rep).
-// pi (optional; the callers that route a batch to k_simple_pi): with the option
-// simple_ports_images on, a batch that holds a NodePorts / ImageLocality pod gets records of the
-// ports-and-images form (pi->form; pi->ports: the pods' masks); pi->na_pod: the pod whose
-// preferred NodeAffinity weights exceed that form's 13 bits (-1 none).  A batch without such a pod
-// is built exactly as without pi.
+// What a podset's k_simple / k_spread records carry beside the SPod / GPod records themselves.
+// form: what simple_form decided.  build_spods fills ports (the pods' masks, in the ports-and-images
+// forms) and, where it refuses, the pod that does not fit the form and why (fail_pod -1: programs).
 struct PiRecords {
-  bool form = false;
-  int na_pod = -1;
+  Form form = FORM_PLAIN;
+  int fail_pod = -1;
+  PodMisfit misfit = POD_FITS;
   std::vector<SPort> ports;
-  // the volumes form (option simple_volumes, a variant of that form; build_spods' `va`): some pod
-  // has a volume program and vol_form_admit took the batch (vol; vols: the pods' SVol records,
-  // vol_add: what their commits can add per limit key), or refused it (vol_code: the GP_VOL_*
-  // reason, vol_pod: the pod it names)
-  bool vol = false;
+  // vol_form_admit's part: it took the batch (vols: the pods' SVol records, vol_add: what their commits can add per
+  // limit key), or refused it (vol_code: the GP_VOL_* reason, vol_pod: the pod it names)
   int vol_code = 0, vol_pod = -1;
   std::vector<SVol> vols;
   uint64_t vol_add[SV_KEYS] = {};
@@ -1492,53 +1507,68 @@ void vol_admit_of(const kss_cluster& cl, std::vector<int32_t>& att_max, std::vec
 
 int vol_fields_fit(const uint64_t (&add)[SV_KEYS], const int32_t* att_max, const int32_t* lim_max, int n_keys);
 bool vol_form_admit(const kss_podset* ps, const VolAdmit& A, PiRecords& out);
-// svc (staging only): the option service_ports_images asks for that form as well -- the service
-// grid reads the staged records; which kernel a staged batch runs on still follows
-// simple_ports_images alone (plan_batch).
-// force (a scenario of a sweep in that form, sweep_plan): records of the form whatever the options
-// and the pods say -- one launch serves every scenario, so a scenario without such a pod gets them
-// too, with zero masks.
-// va (the callers that can route a batch to k_simple_vol: kss_plan_podset, stage_spods): with the
-// options simple_ports_images and simple_volumes both on, a batch that holds a pod with a volume
-// program is put to vol_form_admit; admitted, it gets records of the ports-and-images form (whether
-// or not a pod has ports or images) and pi->vols, and no shapes (no table for it).  Refused, or
-// without va, or without such a pod, the batch is built exactly as before.
-bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int* n_shapes = nullptr,
-                 PiRecords* pi = nullptr, bool svc = false, bool force = false, const VolAdmit* va = nullptr) {
+
+// The form of a (validated) podset's k_simple records (r.form; in the volumes form r.vols and r.vol_add too), by who asks:
+//   ASK_BATCH  a batch plan.  Ports-and-images: the option is on and some pod has host ports or images.  Volumes (va:
+//              the asker can route to k_simple_vol): both options on, some pod has a volume program and vol_form_admit
+//              took the batch; refused there (r.vol_code, r.vol_pod: why) the form is as without va.
+//   ASK_STAGE  a stage, whose records the service grid reads as well: the option service_ports_images asks for the
+//              ports-and-images form too (the kernel a staged batch runs on still follows simple_ports_images alone).
+//   ASK_SWEEP  a scenario of a sweep, which decided one form for all and states it in r.form (the volumes form: with
+//              va): one launch serves every scenario, so the records are of that form whatever the options and the
+//              pods say.  False: vol_form_admit refuses the scenario.
+enum FormAsker { ASK_BATCH, ASK_STAGE, ASK_SWEEP };
+bool simple_form(const kss_podset* ps, FormAsker who, const VolAdmit* va, PiRecords& r) {
+  const Form stated = r.form;
+  r = PiRecords{};
+  bool any_pi = false, any_vol = false;
+  for (int i = 0; i < ps->n_pods; i++) {
+    any_pi |= pod_ports_images(ps->pods[i]);
+    any_vol |= ps->pods[i].vol_len > 0;
+  }
+  if (who == ASK_SWEEP) {
+    r.form = stated;
+    if (!form_vol(stated)) return true;
+    if (!any_vol) r.vols.assign((size_t)std::max(ps->n_pods, 1), SVol{});  // (zero records)
+    return !any_vol || vol_form_admit(ps, *va, r);
+  }
+  if (any_pi && (opt(O_SIMPLE_PI) || (who == ASK_STAGE && opt(O_SERVICE_PI)))) r.form = FORM_PI;
+  if (va && opt(O_SIMPLE_PI) && opt(O_SIMPLE_VOL) && any_vol && vol_form_admit(ps, *va, r)) r.form = FORM_VOL;
+  return true;
+}
+
+// Is a staged batch of form f still allowed now?  The options are process-wide: read once at the stage and again
+// here, at the run (plan_batch, svc_start_locked) and by the host-only plans, which so cannot drift from the run.
+// k_simple: the forms on one part, the volumes form under the window only with the option simple_volumes_window.
+bool simple_form_allowed(Form f, bool windowed, bool split) {
+  return (!form_pi(f) || (!split && opt(O_SIMPLE_PI))) &&
+         (!form_vol(f) || (opt(O_SIMPLE_VOL) && (opt(O_SIMPLE_VOL_WIN) || !windowed)));
+}
+
+// k_spread: one part, no PI instantiation of the statistics fold; the window runs under the same options.
+bool spread_form_allowed(Form f, bool split, bool fold) {
+  return (!form_pi(f) || (!split && opt(O_SPREAD_PI) && !fold)) && (!form_vol(f) || opt(O_SPREAD_VOL));
+}
+
+// The service's k_simple-shaped chain: it takes no volume program, in either form.
+bool service_form_allowed(Form f) { return !form_vol(f) && (!form_pi(f) || opt(O_SERVICE_PI)); }
+
+// Compact records of form r.form (simple_form) of every pod of a (validated) podset for k_simple, with r.ports; false
+// when some pod needs another kernel (spread / inter-pod-affinity programs, or fill_spod refuses it).  n_shapes
+// (optional): the batch's resource shapes (SPod::shape, SPod::shape_rep); none in the volumes form (no table for it).
+bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, PiRecords& r, int* n_shapes = nullptr) {
+  const Form f = r.form;
   out.assign((size_t)std::max(ps->n_pods, 1), SPod{});
   if (n_shapes) *n_shapes = 0;
-  bool form = false, vol = false;
-  if (pi) {
-    *pi = PiRecords{};
-    form = force;
-    if (opt(O_SIMPLE_PI) || (svc && opt(O_SERVICE_PI)))
-      for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
-    if (va && force) {  // a scenario of a sweep in the volumes form (sweep_plan): records of the form whatever the
-                        // options say; a scenario without a volume pod gets zero records
-      bool any = false;
-      for (int i = 0; i < ps->n_pods; i++) any |= ps->pods[i].vol_len > 0;
-      if (any && !vol_form_admit(ps, *va, *pi)) return false;  // (pi->vol_code, pi->vol_pod: why)
-      if (!any) pi->vols.assign((size_t)std::max(ps->n_pods, 1), SVol{});
-      pi->vol = vol = true;
-    } else if (va && opt(O_SIMPLE_PI) && opt(O_SIMPLE_VOL)) {
-      bool any = false;
-      for (int i = 0; i < ps->n_pods; i++) any |= ps->pods[i].vol_len > 0;
-      vol = any && vol_form_admit(ps, *va, *pi);
-      form |= vol;
-    }
-    pi->form = form;
-    if (form) pi->ports.assign((size_t)std::max(ps->n_pods, 1), SPort{});
-  }
+  if (form_pi(f)) r.ports.assign((size_t)std::max(ps->n_pods, 1), SPort{});
   for (int i = 0; i < ps->n_pods; i++) {
     const kss_pod& p = ps->pods[i];
     if (p.n_hard | p.n_soft | p.ipa_len) return false;
-    if (!fill_spod(ps, p, n_scalar, out[(size_t)i], form, vol)) {
-      if (form && p.vol_len == 0) {  // the form's own limit: weights the 20-bit field would hold
-        if (pref_weight_sum(ps, p) <= 0xFFFFF) pi->na_pod = i;
-      }
+    if ((r.misfit = fill_spod(ps, p, n_scalar, out[(size_t)i], f))) {
+      r.fail_pod = i;
       return false;
     }
-    if (form) pi->ports[(size_t)i] = SPort{p.port_conflict, p.port_add};
+    if (form_pi(f)) r.ports[(size_t)i] = SPort{p.port_conflict, p.port_add};
   }
   const int n = ps->n_pods;
   std::vector<kss_shape_key> keys((size_t)n);
@@ -1552,7 +1582,7 @@ bool build_spods(const kss_podset* ps, int n_scalar, std::vector<SPod>& out, int
     out[(size_t)i].shape = ids[(size_t)i];
     out[(size_t)i].shape_rep = rep[(size_t)i];
   }
-  if (n_shapes) *n_shapes = vol ? 0 : ns;  // (the volumes form takes no shape table)
+  if (n_shapes) *n_shapes = form_vol(f) ? 0 : ns;  // (the volumes form takes no shape table)
   return true;
 }
 
@@ -1771,7 +1801,6 @@ bool vol_form_admit(const kss_podset* ps, const VolAdmit& A, PiRecords& out) {
     const int k = vol_fields_fit(out.vol_add, A.att_max, A.lim_max, A.n_keys);
     if (k >= 0) return refuse(GP_VOL_FIELD0 + k, first);
   }
-  out.vol = true;
   return true;
 }
 
@@ -1781,38 +1810,37 @@ bool gfail(GpodNeeds& need, int code, int pod) {
   return false;
 }
 
-// The ports-and-images form (option spread_ports_images on and some pod with host ports or image
-// rows: need.pi): such pods are admitted, every record is of that form (fill_spod's 13-bit limit
-// on raw NodeAffinity) and ends in the pod's SPort, one uint4 behind the longest reference list.
-// A batch without such a pod is built exactly as with the option off.
-// The volumes form (option spread_volumes with spread_ports_images, a variant of that form; va / vr: the
-// callers that can route a batch to it -- kss_plan_podset, stage_spods): a batch that holds a pod with a
-// volume program is put to vol_form_admit, the one admission k_simple's volumes form uses.  Admitted
-// (need.vol; vr: the pods' SVol records and per-key adds), every record is of the ports-and-images form and
-// carries the pod's SVol in the four uint4 ahead of its SPort; refused, the batch keeps k_schedule with the
-// limit's own reason.  Without the option, va or such a pod the batch is built exactly as before.
+// The form of a (validated) podset's k_spread records (need.form), or the refusal (need.fail_code,
+// need.fail_pod).  Ports-and-images: the option spread_ports_images is on, the fold off (no PI
+// instantiation of it) and some pod has host ports or image rows.  Volumes (option spread_volumes as
+// well; va / vr: the caller can route a batch to it): some pod has a volume program and vol_form_admit,
+// the one admission k_simple's volumes form uses, took the batch (vr: the pods' SVol records and
+// per-key adds); refused, the batch keeps k_schedule with the limit's own reason.
+bool spread_form(const kss_podset* ps, const VolAdmit* va, PiRecords* vr, GpodNeeds& need) {
+  need = GpodNeeds{};
+  if (!opt(O_SPREAD_PI) || opt(O_FOLD)) return true;
+  int first_vol = -1;
+  for (int i = 0; i < ps->n_pods; i++) {
+    if (pod_ports_images(ps->pods[i])) need.form = FORM_PI;
+    if (ps->pods[i].vol_len > 0 && first_vol < 0) first_vol = i;
+  }
+  if (opt(O_SPREAD_VOL) && va && vr && first_vol >= 0) {
+    *vr = PiRecords{};
+    if (!vol_form_admit(ps, *va, *vr)) return gfail(need, spread_vol_code(vr->vol_code), vr->vol_pod);
+    need.form = FORM_VOL;
+  }
+  return true;
+}
+
+// In the ports-and-images forms every record is of that form (its 13-bit limit on raw NodeAffinity) and ends in the pod's
+// SPort, one uint4 behind the longest reference list; in the volumes form the pod's SVol fills the four uint4 ahead of it.
 bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_t* key_card, const uint32_t* key_flags,
                  const int32_t* key_empty, std::vector<uint4>& words, GpodNeeds& need, const VolAdmit* va = nullptr,
                  PiRecords* vr = nullptr) {
   std::vector<GPod> out((size_t)std::max(ps->n_pods, 1), GPod{});
   std::vector<std::vector<uint32_t>> refs_of((size_t)std::max(ps->n_pods, 1));
-  need = GpodNeeds{};
-  bool pi = false;
-  if (opt(O_SPREAD_PI) && !opt(O_FOLD))  // (no PI instantiation of the statistics fold)
-    for (int i = 0; i < ps->n_pods; i++) pi |= pod_ports_images(ps->pods[i]);
-  bool vol = false;
-  if (opt(O_SPREAD_PI) && !opt(O_FOLD) && opt(O_SPREAD_VOL) && va && vr) {
-    int first = -1;
-    for (int i = 0; i < ps->n_pods && first < 0; i++)
-      if (ps->pods[i].vol_len > 0) first = i;
-    if (first >= 0) {
-      *vr = PiRecords{};
-      if (!vol_form_admit(ps, *va, *vr)) return gfail(need, spread_vol_code(vr->vol_code), vr->vol_pod);
-      pi = vol = true;
-    }
-  }
-  need.pi = pi;
-  need.vol = vol;
+  if (!spread_form(ps, va, vr, need)) return false;
+  const bool pi = form_pi(need.form), vol = form_vol(need.form);
   std::vector<int32_t> local;  // count row -> resident index (-1 none)
   auto res_of = [&](int rowid) -> int {
     if ((size_t)rowid >= local.size()) local.resize((size_t)rowid + 1, -1);
@@ -1826,11 +1854,8 @@ bool build_gpods(const kss_podset* ps, int n_scalar, int n_classes, const int32_
     const kss_pod& p = ps->pods[i];
     GPod& g = out[(size_t)i];
     std::vector<uint32_t>& R = refs_of[(size_t)i];
-    if ((!pi && pod_ports_images(p)) || (!vol && p.vol_len > 0)) return gfail(need, GP_PORTS_IMAGES, i);
-    if (!fill_spod(ps, p, n_scalar, g.dyn, pi, vol)) {
-      const int64_t wsum = pref_weight_sum(ps, p);  // the form's own limit, or weights no static word holds
-      return gfail(need, pi && wsum <= 0xFFFFF ? GP_SPREAD_PI_NA_WEIGHTS : GP_NA_WEIGHTS, i);
-    }
+    static const int code[POD_N] = {GP_OK, GP_PORTS_IMAGES, GP_PORTS_IMAGES, GP_NA_WEIGHTS, GP_SPREAD_PI_NA_WEIGHTS};
+    if (const PodMisfit m = fill_spod(ps, p, n_scalar, g.dyn, need.form)) return gfail(need, code[m], i);
     if (p.n_hard > MAXH || p.n_soft > MAXS) return gfail(need, GP_CONSTRAINTS, i);
     g.pflags = (int32_t)p.flags;
     g.n_hard = p.n_hard;
@@ -3319,17 +3344,17 @@ static bool same_profile(const kss_profile& a, const kss_profile& b) {
 static int simple_cap(const Geometry& g) { return g.npt * g.threads; }
 
 // The loop kernel's dynamic LDS: the table loop's (n_shapes > 0), k_simple_vol's, k_simple_pi's, k_simple's.
-static size_t simple_lds(int cap, int nsc, bool pi, bool vol, int n_shapes = 0) {
-  return n_shapes > 0 ? simple_lds_bytes(cap, 0, n_shapes)
-         : vol        ? simple_lds_bytes_vol(cap, nsc)
-         : pi         ? simple_lds_bytes_pi(cap, nsc)
-                      : simple_lds_bytes(cap, nsc);
+static size_t simple_lds(int cap, int nsc, Form f, int n_shapes = 0) {
+  return n_shapes > 0  ? simple_lds_bytes(cap, 0, n_shapes)
+         : form_vol(f) ? simple_lds_bytes_vol(cap, nsc)
+         : form_pi(f)  ? simple_lds_bytes_pi(cap, nsc)
+                       : simple_lds_bytes(cap, nsc);
 }
 
-static bool simple_fits(const Geometry& g, int nsc, bool pi = false, bool vol = false) {
+static bool simple_fits(const Geometry& g, int nsc, Form f) {
   const int pf_n = g.threads > 64 ? g.threads - 64 : g.threads;  // prefetch lanes (kss_simple.cuh)
   return g.W <= 64 * SX_CHUNKS && g.npt <= KSS_MAX_NPT && (simple_cap(g) + pf_n - 1) / pf_n <= PF_MAX &&
-         simple_lds(simple_cap(g), nsc, pi, vol) <= KSS_LDS_BUDGET;
+         simple_lds(simple_cap(g), nsc, f) <= KSS_LDS_BUDGET;
 }
 
 // k_simple's shape table (k_simple_tab) for a batch of n_shapes resource shapes on geometry g:
@@ -3433,7 +3458,7 @@ static void static_rows(const Geometry& g, const XPeers& X, int max_nodes, int& 
 // k_static over pods [k0, k1) x rows [n_lo, n_hi) of n_jobs jobs; max_keys: the jobs' largest label-key count
 // (the LDS label copy when it is at most STATIC_LKEYS)
 static void launch_static(hipStream_t st, bool def, const DevJob* jobs, const kss_profile& pr, int n_jobs, int k0, int k1,
-                          int n_lo, int n_hi, int max_keys, int row0 = 0, bool pi = false) {
+                          int n_lo, int n_hi, int max_keys, int row0 = 0, Form f = FORM_PLAIN) {
   const int lk = max_keys > 0 && max_keys <= STATIC_LKEYS ? max_keys : 0;
   // pods per block: with the LDS label copy, enough pods to amortise loading it (C5: 64 pods of
   // 1,000 nodes per block; r6c: 8 / 16 / 32 / 64 within 1 % of each other)
@@ -3442,9 +3467,9 @@ static void launch_static(hipStream_t st, bool def, const DevJob* jobs, const ks
   const dim3 sgrid((unsigned)(std::max(n_hi - n_lo, 1) + 1023) / 1024, (unsigned)((k1 - k0 + ppb - 1) / ppb),
                    (unsigned)n_jobs);
   const size_t sh = sizeof(int32_t) * 1024 * (size_t)lk;
-  // pi: the ports-and-images form of the word (k_simple_pi reads it)
-  const void* fn = pi ? (def ? (const void*)k_static_pi<true> : (const void*)k_static_pi<false>)
-                      : (def ? (const void*)k_static<true> : (const void*)k_static<false>);
+  // the ports-and-images forms: that form of the word (k_simple_pi reads it)
+  const void* fn = form_pi(f) ? (def ? (const void*)k_static_pi<true> : (const void*)k_static_pi<false>)
+                              : (def ? (const void*)k_static<true> : (const void*)k_static<false>);
   void* args[] = {(void*)&jobs, (void*)&pr, (void*)&k0, (void*)&k1, (void*)&n_lo, (void*)&n_hi, (void*)&lk, (void*)&row0, (void*)&ppb};
   (void)hipLaunchKernel(fn, sgrid, dim3(256), args, sh, st);  // (the callers read hipGetLastError)
 }
@@ -3489,10 +3514,11 @@ static int launch_chunk(hipStream_t st, const LoopLaunch& L, const void* fn, dim
 }
 
 // k_simple's family (the sweeps' and the volumes form's kernels are defined at the end of this file).
-static const void* simple_fn(bool def, bool win, bool pi, bool vol, bool sweep, bool tab, bool flat) {
-  if (vol && sweep) return simple_vol_sweep_fn(def);
+static const void* simple_fn(bool def, bool win, Form f, bool sweep, bool tab, bool flat) {
+  const bool pi = form_pi(f);
+  if (form_vol(f) && sweep) return simple_vol_sweep_fn(def);
   if (pi && sweep) return simple_pi_sweep_fn(def);
-  if (vol) return simple_vol_fn(def, win);
+  if (form_vol(f)) return simple_vol_fn(def, win);
   if (flat) return pi ? (const void*)k_simple_tab_flat_pi : (const void*)k_simple_tab_flat;
   if (tab) return pi ? (const void*)k_simple_tab_pi : (const void*)k_simple_tab;
   if (pi)
@@ -3513,35 +3539,48 @@ struct SimpleLaunch : LoopLaunch {
   hipStream_t st2 = nullptr;
   std::vector<hipEvent_t>* pev = nullptr;
   bool flat = false;   // the table loop's flat exchange (the caller checked flat_exchange_ok; one job, one part)
-  // the ports-and-images form (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
+  Form form = FORM_PLAIN;  // the loop kernel's form, which says which of the three pointers below it reads
+  bool sweep = false;      // a scenario sweep's launch (many jobs).  No table, no window, no split and no XCD-local grid
+  // the ports-and-images forms (one job): k_static_pi + k_simple_pi, or, with n_shapes > 0 (an
   // image-only batch; the caller checked), + k_simple_tab_pi / k_simple_tab_flat_pi, which read no sports
   const SPort* sports = nullptr;
-  // ... of a sweep (many jobs; pod_off: every job's first mask in sports): k_static_pi +
-  // k_simple_pi_sweep.  No table, no window, no split and no XCD-local grid: sweeps pass none of those.
+  // ... of a sweep (pod_off: every job's first mask in sports): k_static_pi + k_simple_pi_sweep
   const int32_t* pod_off = nullptr;
   // the volumes form (one job; vl: the launch block on the device, vol_pack_state): k_static_pi + k_static_vol +
   // k_simple_vol per chunk, then the packed attached counts back into vol_attached and the pods' own rows into
   // vol_count (k_vol_unpack, k_vol_counts).  No table, no split; the window as the ports-and-images form runs it.
-  // ... of a sweep (pod_off as above, vl: SVolLaunch[n_jobs], each with its scenario's columns and records):
+  // ... of a sweep (vl: SVolLaunch[n_jobs], each with its scenario's columns and records):
   // + k_simple_vol_sweep; the columns are the sweep's own mutable state, so nothing is written back.
   const SVolLaunch* vl = nullptr;
 };
 
+// What the loop kernel takes behind the 13 arguments every kernel of the family has (into a[13..]):
+//   k_simple, the four table kernels   none
+//   k_simple_pi                        sports
+//   k_simple_pi_sweep                  sports, pod_off
+//   k_simple_vol                       sports, vl
+//   k_simple_vol_sweep                 sports, pod_off, vl
+static void simple_tail_args(const SimpleLaunch& L, void** a) {
+  if (form_pi(L.form)) *a++ = (void*)&L.sports;
+  if (form_pi(L.form) && L.sweep) *a++ = (void*)&L.pod_off;
+  if (form_vol(L.form)) *a++ = (void*)&L.vl;
+}
+
 static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
   const Geometry& g = L.g;
   const int n_jobs = L.n_jobs, n_pods_max = L.n_pods, chunk = L.chunk;
-  const bool vol = L.vl != nullptr, vol_sweep = vol && L.pod_off != nullptr;
-  if (vol && !vol_sweep && (!L.sports || L.n_shapes > 0 || L.split || n_jobs != 1 || L.st2))
+  const bool pi = form_pi(L.form), vol = form_vol(L.form), sweep = L.sweep;
+  // the pointers the stated form reads, and what it does not run with
+  if (vol && !sweep && (!L.vl || !L.sports || L.n_shapes > 0 || L.split || n_jobs != 1 || L.st2))
     return fail(KSS_E_INVAL, "volumes form: one job of the ports-and-images form, no table or split");
-  if (vol_sweep && (!L.sports || L.st2)) return fail(KSS_E_INVAL, "sweep volumes form: the ports-and-images sweep, one stream");
-  const bool pi = L.sports != nullptr, pi_sweep = pi && L.pod_off != nullptr;
-  if (pi_sweep && (L.n_shapes > 0 || L.k_find > 0 || L.split || L.xcd || L.nsc != 0))
+  if (vol && sweep && (!L.vl || !L.sports || L.st2)) return fail(KSS_E_INVAL, "sweep volumes form: the ports-and-images sweep, one stream");
+  if (pi && sweep && (!L.sports || !L.pod_off || L.n_shapes > 0 || L.k_find > 0 || L.split || L.xcd || L.nsc != 0))
     return fail(KSS_E_INVAL, "sweep ports-and-images form: no table, window, split or XCD-local grid");
   int cap = simple_cap(g);
   const bool def = same_profile(*L.prof, default_profile_c());
   const bool win = L.k_find > 0;
   const bool tab = L.n_shapes > 0 && def && !win && L.nsc == 0;
-  const size_t shmem = simple_lds(cap, L.nsc, pi, vol, tab ? L.n_shapes : 0);
+  const size_t shmem = simple_lds(cap, L.nsc, L.form, tab ? L.n_shapes : 0);
   const bool flat = L.flat && tab && n_jobs == 1 && !(L.split && L.split->X.n > 1);
   // its granules (2 x E x SXF_VALS) and the XCD claim counters behind them lie inside what is zeroed
   if (flat && L.gran_bytes / 8 < 2 * (size_t)g.W * (size_t)(g.threads / 64) * SXF_VALS + 1)
@@ -3550,7 +3589,7 @@ static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
   XPeers X = L.split ? L.split->X : XPeers{};
   const bool sp_grid = X.n > 1;
   bool xcd = L.xcd && !sp_grid && n_jobs == 1 && L.gran;
-  const void* fn = simple_fn(def, win, pi, vol, L.pod_off != nullptr, tab, flat);
+  const void* fn = simple_fn(def, win, L.form, sweep, tab, flat);
   const dim3 grid((unsigned)(n_jobs * (sp_grid ? X.wl : g.W)));
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   kss_profile pr = *L.prof;
@@ -3568,7 +3607,7 @@ static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
     // (*pev)[2i]: k_static of chunk i done (st2), (*pev)[2i+1]: k_simple of chunk i done (st)
     HIP_TRY(hipEventRecord((*pev)[1], st));  // st's work so far (the reset) before st2 writes the table
     HIP_TRY(hipStreamWaitEvent(L.st2, (*pev)[1], 0));
-    launch_static(L.st2, def, L.jobs, pr, n_jobs, 0, std::min(n_pods_max, chunk), n_lo, n_hi, L.n_keys, 0, pi);
+    launch_static(L.st2, def, L.jobs, pr, n_jobs, 0, std::min(n_pods_max, chunk), n_lo, n_hi, L.n_keys, 0, L.form);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord((*pev)[0], L.st2));
   }
@@ -3581,12 +3620,12 @@ static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
       if (k1 < n_pods_max) {  // the next chunk's, into the other half, once chunk ci-1 no longer reads it
         if (ci > 0) HIP_TRY(hipStreamWaitEvent(L.st2, (*pev)[2 * (ci - 1) + 1], 0));
         launch_static(L.st2, def, L.jobs, pr, n_jobs, k1, std::min(n_pods_max, k1 + chunk), n_lo, n_hi, L.n_keys,
-                      ((ci + 1) & 1) * chunk, pi);
+                      ((ci + 1) & 1) * chunk, L.form);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord((*pev)[2 * (ci + 1)], L.st2));
       }
     } else {
-      launch_static(st, def, L.jobs, pr, n_jobs, k0, k1, n_lo, n_hi, L.n_keys, 0, pi);
+      launch_static(st, def, L.jobs, pr, n_jobs, k0, k1, n_lo, n_hi, L.n_keys, 0, L.form);
       HIP_TRY(hipGetLastError());
       if (vol) {  // VolumeBinding / VolumeZone verdicts into the words just written
         launch_static_vol(st, L.jobs, pr, k0, k1, n_lo, n_hi, L.vl, n_jobs);
@@ -3602,10 +3641,9 @@ static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
       HIP_TRY(dev_zero(L.gran, L.gran_bytes, st));
     }
     unsigned long long* sp = k0 == 0 ? L.stamps : nullptr;
-    void* args[] = {(void*)&L.jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
-                    (void*)&gc,     (void*)&L.err, (void*)&sp, (void*)&X, (void*)&epoch0, (void*)&row0, (void*)&last_arg,
-                    (void*)&L.sports, vol && !vol_sweep ? (void*)&L.vl : (void*)&L.pod_off,
-                    (void*)&L.vl};  // (k_simple_pi's trailing argument, k_simple_pi_sweep's / k_simple_vol's two, k_simple_vol_sweep's three; the other kernels take 13)
+    void* args[16] = {(void*)&L.jobs, (void*)&pr, (void*)&W,  (void*)&cap, (void*)&k0,     (void*)&k1,
+                      (void*)&gc,     (void*)&L.err, (void*)&sp, (void*)&X, (void*)&epoch0, (void*)&row0, (void*)&last_arg};
+    simple_tail_args(L, args + 13);
     if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci], st));
     if (int rc = launch_chunk(st, L, fn, grid, shmem, args, X, xcd)) return rc;
     if (L.ev) HIP_TRY(hipEventRecord(L.ev[2 * ci + 1], st));
@@ -3614,7 +3652,7 @@ static int launch_simple(hipStream_t st, const SimpleLaunch& L) {
   hipLaunchKernelGGL(k_counts, dim3((unsigned)((n_pods_max + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, L.jobs, 0,
                      n_pods_max);
   HIP_TRY(hipGetLastError());
-  if (vol && !vol_sweep) {
+  if (vol && !sweep) {
     launch_vol_writeback(st, L.jobs, L.max_nodes, n_pods_max, L.vl);
     HIP_TRY(hipGetLastError());
   }
@@ -3632,7 +3670,8 @@ static int spread_cap(const Geometry& g, size_t N) {
 }
 
 static size_t spread_lds(const Geometry& g, const GpodNeeds& q, int n_keys, int n_res, size_t N, int nsc) {
-  return spread_lds_bytes(spread_cap(g, N), q.bins_cap, n_keys, n_res, q.gq, nsc, opt(O_FOLD) != 0, q.pi, q.vol);
+  return spread_lds_bytes(spread_cap(g, N), q.bins_cap, n_keys, n_res, q.gq, nsc, opt(O_FOLD) != 0, form_pi(q.form),
+                          form_vol(q.form));
 }
 
 static bool spread_fits(const Geometry& g, const GpodNeeds& q, int n_keys, int n_res, size_t N, int nsc) {
@@ -3646,20 +3685,20 @@ static bool spread_fits(const Geometry& g, const GpodNeeds& q, int n_keys, int n
 // each shard's last epilogue (int), the diagnosis list, the shadow copy of the node state.
 struct HandoffLayout {
   size_t o_xcc, o_diag, o_shadow, words;
-  // pi: the UsedPorts column behind the scalar columns; vol: used and the two att words behind that (lim is read-only)
-  HandoffLayout(int W, int n_res, int N, int nsc, bool pi = false, bool vol = false) {
+  // the ports-and-images forms: the UsedPorts column behind the scalar columns; volumes: used and the two att words behind that (lim is read-only)
+  HandoffLayout(int W, int n_res, int N, int nsc, Form f) {
     o_xcc = 2 * (size_t)W;
     o_diag = o_xcc + ((size_t)W + 1) / 2;
     o_shadow = (o_diag + 1 + (size_t)HANDOFF_DIAG * HANDOFF_DIAG_W + 15) / 16 * 16;
-    words = o_shadow + (6 + (size_t)std::max(n_res, 0) + (size_t)std::max(nsc, 0) + (pi ? 1 : 0) + (vol ? 3 : 0)) *
+    words = o_shadow + (6 + (size_t)std::max(n_res, 0) + (size_t)std::max(nsc, 0) + (form_pi(f) ? 1 : 0) + (form_vol(f) ? 3 : 0)) *
                            (size_t)std::max(N, 1);
   }
 };
 
 // k_spread's family; the window (default profile, no fold) and the ports-and-images form (no fold; defined at
 // the end of this file) have their own instantiations.  launch_spread refuses the combinations that have none.
-static const void* spread_fn(bool def, bool fold, bool lb, bool win, bool pi, bool vol) {
-  if (vol) return spread_vol_fn(def, lb, win);
+static const void* spread_fn(bool def, bool fold, bool lb, bool win, Form f) {
+  if (form_vol(f)) return spread_vol_fn(def, lb, win);
   const void* fn = lb ? (def ? (fold ? (const void*)k_spread<true, true, 256, false> : (const void*)k_spread<true, false, 256, false>)
                              : (fold ? (const void*)k_spread<false, true, 256, false> : (const void*)k_spread<false, false, 256, false>))
                       : (def ? (fold ? (const void*)k_spread<true, true, KSS_MAX_THREADS, false>
@@ -3667,7 +3706,7 @@ static const void* spread_fn(bool def, bool fold, bool lb, bool win, bool pi, bo
                              : (fold ? (const void*)k_spread<false, true, KSS_MAX_THREADS, false>
                                      : (const void*)k_spread<false, false, KSS_MAX_THREADS, false>));
   if (win) fn = lb ? (const void*)k_spread<true, false, 256, true> : (const void*)k_spread<true, false, KSS_MAX_THREADS, true>;
-  if (pi) fn = spread_pi_fn(def, lb, win);
+  if (form_pi(f)) fn = spread_pi_fn(def, lb, win);
   return fn;
 }
 
@@ -3676,7 +3715,7 @@ struct SpreadLaunch : LoopLaunch {
   const GpodNeeds* q = nullptr;  // the batch's needs (with the window's count area when k_find > 0)
   int n_res = 0;                 // its resident count rows
   unsigned long long *ck = nullptr, *ck_seq = nullptr;  // the checked hand-off's buffer (HandoffLayout), its tag counter
-  // the volumes form (q->vol; vl: the launch block on the device, vol_pack_state): k_static_pi + k_static_vol +
+  // the volumes form (q->form; vl: the launch block on the device, vol_pack_state): k_static_pi + k_static_vol +
   // k_spread_vol per chunk, the mutable columns carried through the checked hand-off, then the packed attached
   // counts back into vol_attached and the pods' own rows into vol_count (k_vol_unpack, k_vol_counts)
   const SVolLaunch* vl = nullptr;
@@ -3703,13 +3742,14 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
   const bool fold = opt(O_FOLD) != 0;
   const bool lb = g.threads <= 256 && opt(O_SPREAD_LB256);
   if (L.k_find > 0 && (!def || fold)) return fail(KSS_E_INVAL, "k_spread window: default profile, no statistics fold");
-  // the ports-and-images form (build_gpods need.pi; plan_batch checked: one part, no fold): k_static_pi's words
-  if (q.pi && (fold || L.split)) return fail(KSS_E_INVAL, "k_spread ports-and-images form: one part, no statistics fold");
-  if (q.vol && (!q.pi || !L.vl)) return fail(KSS_E_INVAL, "k_spread volumes form: the ports-and-images form with its launch block");
+  // the ports-and-images forms (spread_form; plan_batch checked: one part, no fold): k_static_pi's words
+  const bool pi = form_pi(q.form), vol = form_vol(q.form);
+  if (pi && (fold || L.split)) return fail(KSS_E_INVAL, "k_spread ports-and-images form: one part, no statistics fold");
+  if (vol && !L.vl) return fail(KSS_E_INVAL, "k_spread volumes form: the ports-and-images form with its launch block");
   XPeers X = L.split ? L.split->X : XPeers{};
   const bool sp_grid = X.n > 1;
   bool xcd = L.xcd && !sp_grid && L.gran && g.W > 1;
-  const void* fn = spread_fn(def, fold, lb, L.k_find > 0, q.pi, q.vol);
+  const void* fn = spread_fn(def, fold, lb, L.k_find > 0, q.form);
   const dim3 grid((unsigned)(sp_grid ? X.wl : g.W));
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   // many shards on one part: the two-level selectHost exchange, its area at the end of the
@@ -3722,7 +3762,7 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
   int W = g.W, n_lo = 0, n_hi = 0;
   static_rows(g, X, L.max_nodes, n_lo, n_hi);
   // the checked node-state hand-off (HandoffCheck): tags increase over the context's life
-  const HandoffLayout hl(g.W, L.n_res, L.max_nodes, L.nsc, q.pi, q.vol);
+  const HandoffLayout hl(g.W, L.n_res, L.max_nodes, L.nsc, q.form);
   auto handoff = [&](unsigned long long expect, unsigned long long write) {
     HandoffCheck hc{};
     if (!L.ck || !L.ck_seq) return hc;
@@ -3736,9 +3776,9 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
   for (int k0 = 0; k0 < L.n_pods; k0 += L.chunk) {
     int k1 = std::min(L.n_pods, k0 + L.chunk);
     const int ci = k0 / std::max(L.chunk, 1);
-    launch_static(st, def, L.jobs, pr, 1, k0, k1, n_lo, n_hi, L.n_keys, 0, q.pi);
+    launch_static(st, def, L.jobs, pr, 1, k0, k1, n_lo, n_hi, L.n_keys, 0, q.form);
     HIP_TRY(hipGetLastError());
-    if (q.vol) {  // VolumeBinding / VolumeZone verdicts into the words just written (the policy bits stay)
+    if (vol) {  // VolumeBinding / VolumeZone verdicts into the words just written (the policy bits stay)
       launch_static_vol(st, L.jobs, pr, k0, k1, n_lo, n_hi, L.vl, 1);
       HIP_TRY(hipGetLastError());
     }
@@ -3765,12 +3805,12 @@ static int launch_spread(hipStream_t st, const SpreadLaunch& L) {
   }
   if (L.ck && L.ck_seq && L.n_pods > 0) {  // the last chunk's write-back, checked (nothing repairs it)
     const HandoffCheck hc = handoff(*L.ck_seq, 0ull);
-    if (q.vol) hipLaunchKernelGGL(k_handoff_final_vol, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err, L.vl);
-    else if (q.pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
+    if (vol) hipLaunchKernelGGL(k_handoff_final_vol, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err, L.vl);
+    else if (pi) hipLaunchKernelGGL(k_handoff_final_pi, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
     else hipLaunchKernelGGL(k_handoff_final, grid, dim3(256), 0, st, L.jobs, W, sp_grid ? X.w_off : 0, L.n_res, hc, L.err);
     HIP_TRY(hipGetLastError());
   }
-  if (q.vol && L.n_pods > 0) {  // vol_attached and vol_count as k_schedule would have left them
+  if (vol && L.n_pods > 0) {  // vol_attached and vol_count as k_schedule would have left them
     launch_vol_writeback(st, L.jobs, L.max_nodes, L.n_pods, L.vl);
     HIP_TRY(hipGetLastError());
   }
@@ -3808,8 +3848,8 @@ static bool spread_window_profile_ok(const kss_profile& p) { return !opt(O_FOLD)
 // What plan_batch decides for one batch; launch_batch and finish_batch read nothing else about the route.
 struct BatchPlan {
   Geometry g;
-  bool simple = false, simple_pi = false, simple_vol = false, spread = false;  // k_simple and its forms, k_spread
-  bool spread_vol = false;  // ... on its volumes form (option spread_volumes)
+  bool simple = false, spread = false;  // k_simple, k_spread
+  Form form = FORM_PLAIN;               // the chosen loop kernel's form (FORM_PLAIN on k_schedule)
   bool xcd_simple = false, xcd_spread = false, tab = false, flat = false;  // XCD-local grid; shape table, flat exchange
   bool window = false, spread_win = false;  // percentageOfNodesToScore < 100; ... and k_find < N (the search can stop early)
   int k_find = 0, win_find = 0;             // numFeasibleNodesToFind (N without a window); 0 unless k_find < N
@@ -3832,6 +3872,7 @@ struct BatchLaunched {
   int n_chunks = 0;
 };
 
+static int vol_pack_state(kss_ctx* ctx, Form f, bool& ok);
 // Which kernel, geometry and form pods [0, n) run on, or the refusal.  Assigns no granule epoch and writes no
 // ctx->last_* field: a refused batch leaves the context as it was.  Its only device work is vol_pack_state.
 static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, bool record, bool keep_norm, uint32_t flags,
@@ -3872,18 +3913,10 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   const bool loop_ok = !window_names_block(windowed, ctx->staged_names) && !nomq && staged && commit && !record && !keep_norm &&
                        scalar_fast_ok(ctx->prof, ctx->dc.n_scalar) && ctx->small_values &&
                        f64_exact(ctx->f64_cluster, ctx->f64_pods, n) && !ctx->no_simple && !(flags & KSS_SCHED_GENERAL_KERNEL);
-  bool simple_ok = loop_ok && ctx->spod_ok && !need.general &&
-                   // the ports-and-images form: one part, and the option still on (it is process-wide)
-                   (!ctx->spod_pi || (!split && opt(O_SIMPLE_PI))) &&
-                   // its volumes form: that option too, and the window only with simple_volumes_window
-                   (!ctx->spod_vol || (opt(O_SIMPLE_VOL) && (opt(O_SIMPLE_VOL_WIN) || !windowed)));
-  // ... and the packed fields cannot overflow (vol_form_admit's condition 4) on the columns as they
-  // are now: packed here, before the batch's first launch
-  if (simple_ok && ctx->spod_vol) {
-    bool fits = false;
-    if (int rc = vol_pack_state(ctx, fits)) return rc;
-    simple_ok = fits;
-  }
+  bool simple_ok = loop_ok && ctx->spod_ok && !need.general && simple_form_allowed(ctx->spod_form, windowed, split);
+  // ... and, in the volumes form, the packed fields cannot overflow (vol_form_admit's condition 4) on
+  // the columns as they are now: packed here, before the batch's first launch
+  if (int rc = vol_pack_state(ctx, ctx->spod_form, simple_ok)) return rc;
   // a k_simple-eligible batch keeps W within k_simple's exchange sweep (64 * SX_CHUNKS
   // shards): at 100k nodes, 98-128 k_simple shards beat 256 k_schedule shards (69.8k
   // against 44.2k pods/s)
@@ -3903,17 +3936,8 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   // PreFilterResult list, the statistics fold off (one part or a split grid)
   bool spread_ok = loop_ok && (!windowed || spread_window_profile_ok(ctx->prof)) && ctx->gpod_ok && need.general &&
                    !ctx->no_spread && spread_bounds_ok(ctx->gneed, pl.count_total, pl.cell_total, (int)N) &&
-                   // the ports-and-images form: one part, no fold, and the option still on (it is process-wide)
-                   (!ctx->gpod_pi || (!split && opt(O_SPREAD_PI) && !opt(O_FOLD))) &&
-                   // its volumes form: that option too (the window runs under the same option)
-                   (!ctx->gpod_vol || opt(O_SPREAD_VOL));
-  // ... and the packed fields cannot overflow (vol_form_admit's condition 4) on the columns as they are now:
-  // packed here, before the batch's first launch, as for k_simple's volumes form
-  if (spread_ok && ctx->gpod_vol) {
-    bool fits = false;
-    if (int rc = vol_pack_state(ctx, fits)) return rc;
-    spread_ok = fits;
-  }
+                   spread_form_allowed(ctx->gpod_form, split, opt(O_FOLD) != 0);  // (as for k_simple)
+  if (int rc = vol_pack_state(ctx, ctx->gpod_form, spread_ok)) return rc;  // (as for k_simple's volumes form)
   if (opt(O_TRACE_PATH))  // diagnosis: why a batch with programs is (not) on k_spread
     fprintf(stderr,
             "kss path: staged=%d gpod_ok=%d commit=%d record=%d general=%d scalar=%d small=%d f64=%d bounds=%d "
@@ -3934,8 +3958,7 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   Geometry& g = pl.g;
   if (!pick_geometry((int)N, W, ctx->pref_threads, g)) return fail(KSS_E_UNSUPPORTED, "no geometry for this cluster");
   const int nsc = ctx->dc.n_scalar;
-  const bool simple = pl.simple = simple_ok && simple_fits(g, nsc, ctx->spod_pi, ctx->spod_vol);
-  pl.simple_pi = simple && ctx->spod_pi, pl.simple_vol = simple && ctx->spod_vol;
+  const bool simple = pl.simple = simple_ok && simple_fits(g, nsc, ctx->spod_form);
   const int n_res = pl.n_res = (int)ctx->gneed.res_rows.size();
   pl.q = &ctx->gneed;
   auto fits = [&](const Geometry& g2) { return spread_fits(g2, ctx->gneed, ctx->dc.n_keys, n_res, N, nsc); };
@@ -3973,7 +3996,7 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   // XCD-local k_spread: the shards on one XCD when they fit its CUs
   if (spread && !simple && xcd_ok) pl.xcd_spread = g.W > xcd_w ? repick(xcd_w, SPREAD_PREF_THREADS) : g.W > 1;
   pl.spread = spread, pl.xcd_simple = simple && xcd_try && g.W > 1;
-  pl.spread_vol = spread && ctx->gpod_vol;
+  pl.form = simple ? ctx->spod_form : (spread ? ctx->gpod_form : FORM_PLAIN);
   if (split && !pl.loop())
     return fail(KSS_E_UNSUPPORTED, spread_ok ? "split grid: a k_spread shard exceeds LDS (more shards per part)"
                                              : "split grid: the batch needs k_schedule (kss_plan_podset)");
@@ -4005,10 +4028,10 @@ static int plan_batch(kss_ctx* ctx, const PlanNeeds& need, int n, bool commit, b
   // (the ports-and-images form: an image-only batch, option table_images -- k_simple_tab_pi;
   // UsedPorts is not a function of the resource shape, so a host-port pod keeps the batch on k_simple_pi)
   // (the volumes form: never -- its batches have no shapes)
-  pl.tab = simple && !pl.simple_vol && (!pl.simple_pi || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
+  pl.tab = simple && !form_vol(pl.form) && (!form_pi(pl.form) || (opt(O_TABLE_IMAGES) && !ctx->spod_ports)) && opt(O_SHAPE_TABLE) &&
            n == ctx->staged_n && shape_table_ok(g, (int)N, ctx->spod_shapes, ctx->prof, pl.win_find, nsc);
   pl.flat = pl.tab && flat_exchange_ok(g, (int)N, ctx->prof, split);
-  if (simple) pl.lds = simple_lds(simple_cap(g), nsc, pl.simple_pi, pl.simple_vol, pl.tab ? ctx->spod_shapes : 0);
+  if (simple) pl.lds = simple_lds(simple_cap(g), nsc, pl.form, pl.tab ? ctx->spod_shapes : 0);
   if (spread) pl.lds = spread_lds(g, *pl.q, ctx->dc.n_keys, n_res, N, nsc);
   pl.n = n, pl.commit = commit, pl.record = record, pl.keep_norm = keep_norm;
   pl.general = need.general, pl.sched_bins = std::max(need.bins_cap, 0) + (window ? g.W : 0);
@@ -4133,8 +4156,8 @@ static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, co
   ctx->last_shape[0] = pl.tab ? ctx->spod_shapes : 0;
   ctx->last_shape[1] = pl.tab ? shape_tab_rounds(g.threads / 64, ctx->spod_shapes) : 0;
   ctx->last_flat[0] = pl.flat ? 1 : 0, ctx->last_flat[1] = pl.flat ? g.W * (g.threads / 64) : 0;
-  ctx->last_simple_form[0] = pl.simple_vol ? 1 : 0, ctx->last_simple_form[1] = simple ? (int)pl.lds : 0;
-  ctx->last_spread_form[0] = spread ? (pl.spread_vol ? 2 : (pl.q->pi ? 1 : 0)) : 0, ctx->last_spread_form[1] = spread ? (int)pl.lds : 0;
+  ctx->last_simple_form[0] = simple && form_vol(pl.form) ? 1 : 0, ctx->last_simple_form[1] = simple ? (int)pl.lds : 0;
+  ctx->last_spread_form[0] = spread ? (int)pl.form : 0, ctx->last_spread_form[1] = spread ? (int)pl.lds : 0;
   if (!loop) {
     rc = launch_schedule(ctx->stream, g, 1, pl.sched_bins, pl.general, ctx->dc.n_keys, jd, ctx->prof, gran, errp, run.stamps,
                          epoch0);
@@ -4155,11 +4178,12 @@ static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, co
       SimpleLaunch S{L};
       S.n_shapes = pl.tab ? ctx->spod_shapes : 0;
       S.flat = pl.flat;
-      S.sports = pl.simple_pi ? (const SPort*)ctx->sport_buf.p : nullptr;
-      S.vl = pl.simple_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
+      S.form = pl.form;
+      S.sports = form_pi(pl.form) ? (const SPort*)ctx->sport_buf.p : nullptr;
+      S.vl = form_vol(pl.form) ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
       rc = launch_simple(ctx->stream, S);
     } else {
-      const HandoffLayout hl(g.W, pl.n_res, (int)N, ctx->dc.n_scalar, ctx->gneed.pi, pl.spread_vol);
+      const HandoffLayout hl(g.W, pl.n_res, (int)N, ctx->dc.n_scalar, pl.form);
       if ((rc = ctx->ck_buf.ensure(sizeof(unsigned long long) * hl.words))) return rc;
       HIP_TRY(dev_zero((unsigned long long*)ctx->ck_buf.p + hl.o_diag, sizeof(unsigned long long), ctx->stream));
       ctx->ck_diag_off = hl.o_diag;
@@ -4167,7 +4191,7 @@ static int launch_batch(kss_ctx* ctx, const BatchPlan& pl, const DevPods& dp, co
       SpreadLaunch G{L};
       G.q = pl.q, G.n_res = pl.n_res;
       G.ck = (unsigned long long*)ctx->ck_buf.p, G.ck_seq = &ctx->ck_seq;
-      G.vl = pl.spread_vol ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
+      G.vl = form_vol(pl.form) ? (const SVolLaunch*)ctx->vol_state_buf.p : nullptr;
       rc = launch_spread(ctx->stream, G);
     }
   }
@@ -4202,7 +4226,7 @@ static int finish_batch(kss_ctx* ctx, const BatchPlan& pl, const BatchLaunched& 
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->last_ms = ms;
   // (the volumes form of k_spread: k_static_pi + k_static_vol + k_spread_vol per chunk, then k_vol_unpack + k_vol_counts)
-  ctx->last_launches = pl.spread_vol ? 3 * run.n_chunks + 2 : (pl.loop() ? 2 * run.n_chunks : 1);
+  ctx->last_launches = pl.spread && form_vol(pl.form) ? 3 * run.n_chunks + 2 : (pl.loop() ? 2 * run.n_chunks : 1);
   ctx->last_loop_ms = pl.loop() ? 0.0 : ms;
   for (int i = 0; i < run.n_chunks; i++) {
     float t = 0;
@@ -4280,28 +4304,38 @@ static int run_single(kss_ctx* ctx, const PlanNeeds& need, const DevPods& dp, in
   return rc;
 }
 
+// The volumes form's launch constants (keyrows, key_on, key_csi, vr_on) from a cluster's row / key dictionaries and the profile.
+static void vol_launch_consts(SVolLaunch& K, const int32_t* row_key, int n_rows, const int32_t* key_plugin, int n_keys,
+                              const kss_profile& prof) {
+  const uint32_t en = prof.filter_enabled;
+  for (int k = 0; k < SV_KEYS; k++) K.keyrows[k] = 0;
+  K.key_on = K.key_csi = 0;
+  for (int r = 0; r < n_rows && r < SV_ROWS; r++) {
+    const int k = row_key[r];
+    if (k >= 0 && k < SV_KEYS) K.keyrows[k] |= 1ull << r;
+  }
+  for (int k = 0; k < n_keys && k < SV_KEYS; k++) {
+    const int pl = key_plugin[k];
+    if ((en >> pl) & 1u) K.key_on |= 1u << k;
+    if (pl == KSS_F_NODE_VOLUME_LIMITS) K.key_csi |= 1u << k;
+  }
+  K.vr_on = (en >> KSS_F_VOLUME_RESTRICTIONS) & 1u;
+}
+
 // The volumes form before a batch's first launch (plan_batch; the staged batch is of the form):
 // the node-state columns packed from the device's vol_count / vol_attached / vol_limit as they are
 // now (k_vol_pack), the launch block uploaded, and vol_form_admit's condition 4 on the maxima the
 // pack reports -- one small read-back and one synchronisation, paid by a batch of the form only.
-// fits false: a field could overflow; nothing was changed and the batch runs on k_schedule.
-static int vol_pack_state(kss_ctx* ctx, bool& fits) {
+// Nothing to do unless the batch is still a candidate (ok) of the volumes form (f).  ok becomes false
+// where a field could overflow: nothing was changed and the batch runs on k_schedule.
+static int vol_pack_state(kss_ctx* ctx, Form f, bool& ok) {
+  if (!ok || !form_vol(f)) return 0;
   const size_t N = (size_t)std::max(ctx->dc.N, 1);
   const VolStateLayout VL(N);
   if (int rc = ctx->vol_state_buf.ensure(VL.bytes)) return rc;
   char* b = (char*)ctx->vol_state_buf.p;
   SVolLaunch K{};
-  const uint32_t en = ctx->prof.filter_enabled;
-  for (int r = 0; r < ctx->dc.n_vol_rows && r < SV_ROWS; r++) {
-    const int k = ctx->vol_row_key_h[(size_t)r];
-    if (k >= 0 && k < SV_KEYS) K.keyrows[k] |= 1ull << r;
-  }
-  for (int k = 0; k < ctx->dc.n_vol_keys && k < SV_KEYS; k++) {
-    const int pl = ctx->vol_key_plugin_h[(size_t)k];
-    if ((en >> pl) & 1u) K.key_on |= 1u << k;
-    if (pl == KSS_F_NODE_VOLUME_LIMITS) K.key_csi |= 1u << k;
-  }
-  K.vr_on = (en >> KSS_F_VOLUME_RESTRICTIONS) & 1u;
+  vol_launch_consts(K, ctx->vol_row_key_h.data(), ctx->dc.n_vol_rows, ctx->vol_key_plugin_h.data(), ctx->dc.n_vol_keys, ctx->prof);
   K.used = (uint64_t*)(b + VL.o_used);
   K.att = (uint64_t*)(b + VL.o_att);
   K.lim = (uint64_t*)(b + VL.o_lim);
@@ -4315,7 +4349,7 @@ static int vol_pack_state(kss_ctx* ctx, bool& fits) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(chk, b + VL.o_chk, sizeof(chk), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  fits = vol_fields_fit(ctx->spod_vol_add, chk, chk + SV_KEYS, ctx->dc.n_vol_keys) < 0;
+  ok = vol_fields_fit(ctx->staged_vol_add, chk, chk + SV_KEYS, ctx->dc.n_vol_keys) < 0;
   return 0;
 }
 
@@ -4343,30 +4377,28 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   va.n_rows = ctx->dc.n_vol_rows;
   va.n_keys = ctx->dc.n_vol_keys;
   va.row_key = ctx->vol_row_key_h.data();
-  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, &ctx->spod_shapes, &pi, /*svc=*/true, false,
-                             (int)ctx->vol_row_key_h.size() == va.n_rows ? &va : nullptr);
-  ctx->spod_pi = ctx->spod_ok && pi.form;
-  ctx->spod_vol = ctx->spod_ok && pi.vol;
-  ctx->svol_host.swap(pi.vols);
-  for (int k = 0; k < SV_KEYS; k++) ctx->spod_vol_add[k] = pi.vol_add[k];
+  const VolAdmit* vap = (int)ctx->vol_row_key_h.size() == va.n_rows ? &va : nullptr;
+  simple_form(ps, ASK_STAGE, vap, pi);
+  ctx->spod_ok = build_spods(ps, ctx->dc.n_scalar, ctx->spod_host, pi, &ctx->spod_shapes);
+  ctx->spod_form = ctx->spod_ok ? pi.form : FORM_PLAIN;
   ctx->spod_ports = false;
   for (const SPort& q : pi.ports) ctx->spod_ports |= (q.conflict | q.add) != 0;
   ctx->sport_host.swap(pi.ports);
-  ctx->gpod_ok = ctx->gpod_pi = ctx->gpod_vol = false;
-  if (!ctx->spod_ok) {  // programs: the resolved records of k_spread
-    PiRecords vr;  // (its volumes form: the same admission, condition 4 at the run as above)
-    ctx->gpod_ok = build_gpods(ps, ctx->dc.n_scalar, ctx->dc.n_classes, ctx->key_card_h.data(), ctx->key_flags_h.data(),
-                               ctx->key_empty_h.data(), ctx->gpod_host, ctx->gneed,
-                               (int)ctx->vol_row_key_h.size() == va.n_rows ? &va : nullptr, &vr);
+  // programs: the resolved records of k_spread (its volumes form: the same admission into the same
+  // records, condition 4 at the run as above)
+  ctx->gpod_ok = !ctx->spod_ok && build_gpods(ps, ctx->dc.n_scalar, ctx->dc.n_classes, ctx->key_card_h.data(),
+                                              ctx->key_flags_h.data(), ctx->key_empty_h.data(), ctx->gpod_host, ctx->gneed, vap, &pi);
+  ctx->gpod_form = ctx->gpod_ok ? ctx->gneed.form : FORM_PLAIN;
+  // the volumes forms: the pods' SVol records for k_static_vol, the per-key adds for vol_pack_state
+  ctx->svol_host.swap(pi.vols);
+  for (int k = 0; k < SV_KEYS; k++) ctx->staged_vol_add[k] = pi.vol_add[k];
+  if (form_vol(ctx->spod_form) || form_vol(ctx->gpod_form)) {
+    if (int rc = ctx->svol_buf.ensure(sizeof(SVol) * ctx->svol_host.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->svol_buf.p, ctx->svol_host.data(), sizeof(SVol) * ctx->svol_host.size(),
+                           hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (!ctx->spod_ok) {
     if (!ctx->gpod_ok) return 0;
-    ctx->gpod_pi = ctx->gneed.pi;
-    if ((ctx->gpod_vol = ctx->gneed.vol)) {  // the pods' SVol records for k_static_vol, the per-key adds for vol_pack_state
-      ctx->svol_host.swap(vr.vols);
-      for (int k = 0; k < SV_KEYS; k++) ctx->spod_vol_add[k] = vr.vol_add[k];
-      if (int rc = ctx->svol_buf.ensure(sizeof(SVol) * ctx->svol_host.size())) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->svol_buf.p, ctx->svol_host.data(), sizeof(SVol) * ctx->svol_host.size(),
-                             hipMemcpyHostToDevice, ctx->stream));
-    }
     int rc = ctx->gpod_buf.ensure(sizeof(uint4) * ctx->gpod_host.size());
     if (rc) return rc;
     if ((rc = ctx->res_buf.ensure(sizeof(int32_t) * std::max<size_t>(ctx->gneed.res_rows.size(), 1)))) return rc;
@@ -4381,14 +4413,9 @@ static int stage_spods(kss_ctx* ctx, const kss_podset* ps) {
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ctx->spod_buf.p, ctx->spod_host.data(), sizeof(SPod) * ctx->spod_host.size(),
                          hipMemcpyHostToDevice, ctx->stream));
-  if (ctx->spod_pi) {
+  if (form_pi(ctx->spod_form)) {
     if ((rc = ctx->sport_buf.ensure(sizeof(SPort) * ctx->sport_host.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->sport_buf.p, ctx->sport_host.data(), sizeof(SPort) * ctx->sport_host.size(),
-                           hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (ctx->spod_vol) {
-    if ((rc = ctx->svol_buf.ensure(sizeof(SVol) * ctx->svol_host.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->svol_buf.p, ctx->svol_host.data(), sizeof(SVol) * ctx->svol_host.size(),
                            hipMemcpyHostToDevice, ctx->stream));
   }
   return 0;
@@ -4961,10 +4988,11 @@ static int svc_start_locked(kss_ctx* ctx) {
   // no extended resources, exact f64 arithmetic, W <= 64 (its exchange:
   // one lane per shard), the node rows cached in LDS (checked below); KSS_SERVICE_GENERAL=1 keeps
   // the general chain, for comparison.  On an XCD-local grid when its shards fit one XCD's CUs.
-  // A staged list of the ports-and-images form (spod_pi) takes it only with the option
-  // service_ports_images on, the static-word table and room for the UsedPorts column (below).
-  // (a staged list of the volumes form, spod_vol, never: that chain takes no volume program)
-  const bool simple_pre = ctx->spod_ok && !ctx->spod_vol && (!ctx->spod_pi || opt(O_SERVICE_PI)) && (!window || !ctx->staged_names) && !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
+  // A staged list of the ports-and-images form takes it only with the option service_ports_images
+  // still on, the static-word table and room for the UsedPorts column (below); one of the volumes
+  // form never (service_form_allowed).
+  const bool simple_pre = ctx->spod_ok && service_form_allowed(ctx->spod_form) && (!window || !ctx->staged_names) &&
+                          !need.general && ctx->dc.n_scalar == 0 && ctx->small_values &&
                           f64_exact(ctx->f64_cluster, ctx->f64_pods, ctx->staged_n) && !opt(O_SERVICE_GENERAL);
   const int xcd_cus = ctx->n_cu / XCD_GRID_MULT;
   // (off by default: the record's stores to host memory from one XCD were slower than the L2
@@ -5040,7 +5068,7 @@ static int svc_start_locked(kss_ctx* ctx) {
   const size_t lds_cached = base + (cache_keys >= 0 ? node_cache_bytes(cap, cache_keys) : 0);
   // (the ports-and-images form keeps 8 more per slot, the UsedPorts column, behind it; that form
   // reads k_static_pi's words and has no inline evaluation of them: no table, no such grid)
-  const size_t pi_col = simple_pre && ctx->spod_pi ? 8 * (size_t)cap : 0;
+  const size_t pi_col = simple_pre && form_pi(ctx->spod_form) ? 8 * (size_t)cap : 0;
   const size_t stat_bytes = sizeof(uint32_t) * (size_t)std::max(ctx->staged_n, 1) * std::max<size_t>(N, 1);
   const bool stat_ok = stat_bytes <= ((size_t)4 << 30) && !opt(O_SVC_NO_STATIC);
   const bool nom_lds_ok = ctx->nom.empty() || lds_cached + 8 * (size_t)cap + pi_col <= KSS_LDS_BUDGET;
@@ -5058,7 +5086,7 @@ static int svc_start_locked(kss_ctx* ctx) {
   HIP_TRY(hipMemcpyAsync(v.job.p, &v.job_host, sizeof(DevJob), hipMemcpyHostToDevice, v.stream));
   if (pre_static) {
     launch_static(v.stream, same_profile(ctx->prof, default_profile_c()), (const DevJob*)v.job.p, ctx->prof, 1, 0,
-                  ctx->staged_n, 0, (int)N, ctx->dc.n_keys, 0, v.pi);
+                  ctx->staged_n, 0, (int)N, ctx->dc.n_keys, 0, v.pi ? FORM_PI : FORM_PLAIN);
     HIP_TRY(hipGetLastError());
   }
   v.W = g.W;
@@ -5443,7 +5471,8 @@ int kss_plan_shapes(const kss_podset* ps, int32_t n_scalar, int32_t* ids, int32_
   std::vector<SPod> sp;
   int ns = 0;
   PiRecords pi;  // (follows the process-wide option simple_ports_images, as kss_plan_podset)
-  if (!build_spods(ps, n_scalar, sp, &ns, &pi)) return fail(KSS_E_UNSUPPORTED, "the batch has no compact records (k_simple does not take it)");
+  simple_form(ps, ASK_BATCH, nullptr, pi);
+  if (!build_spods(ps, n_scalar, sp, pi, &ns)) return fail(KSS_E_UNSUPPORTED, "the batch has no compact records (k_simple does not take it)");
   for (int i = 0; i < ps->n_pods; i++) ids[i] = sp[(size_t)i].shape;
   *n = ns;
   return 0;
@@ -5507,12 +5536,11 @@ struct Packer {
 };
 
 // The read-only part of one scenario: cluster columns except the mutable ones, the pod
-// programs and (simple sweeps) the compact pod records.  pi (a sweep in the ports-and-images form):
-// + the image-score rows.
-// vol (a sweep whose pods hold volume programs, option sweep_volumes): + the volume limits, the row /
-// key dictionaries and the pods' volume entries, which k_schedule and k_static_vol read.
-void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const std::vector<SPod>* spods, DevJob& j,
-                 bool pi = false, bool vol = false) {
+// programs and (simple sweeps) the compact pod records.  A sweep in the ports-and-images forms:
+// + the image-score rows.  In the volumes form (some pod holds a volume program, option
+// sweep_volumes): + the volume limits, the row / key dictionaries and the pods' volume entries,
+// which k_schedule and k_static_vol read.
+void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const std::vector<SPod>* spods, DevJob& j, Form f) {
   const size_t N = (size_t)cl->n_nodes, K = (size_t)cl->n_label_keys;
   DevCluster& c = j.c;
   c.N = cl->n_nodes;
@@ -5545,7 +5573,7 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
   c.nct = nullptr;
   c.nc32 = nullptr;
   c.ncl = nullptr;
-  if (pi) {
+  if (form_pi(f)) {
     c.image_score = P.put(cl->image_score, (size_t)cl->n_images * N);
     c.n_images = cl->n_images;
   }
@@ -5553,7 +5581,7 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
   c.vol_count = c.vol_attached = nullptr;
   c.vol_limit = c.vol_row_key = c.vol_key_plugin = nullptr;
   j.P.vols = nullptr;
-  if (vol) {
+  if (form_vol(f)) {
     c.n_vol_rows = cl->n_vol_rows;
     c.n_vol_keys = cl->n_vol_keys;
     c.vol_limit = P.put(cl->vol_limit, (size_t)cl->n_vol_keys * N);
@@ -5571,18 +5599,18 @@ void pack_inputs(Packer& P, const kss_cluster* cl, const kss_podset* ps, const s
 }
 
 // The mutable columns of one scenario (AssumePod targets): the host image holds the
-// snapshot (the device's pristine copy); the device pointers address the live copy.  pi: + the
-// UsedPorts column (zero without a port dictionary), restored with the rest on every run.
-// vol: + vol_count / vol_attached (k_schedule's AssumePod targets).
-void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j, bool pi = false, bool vol = false) {
+// snapshot (the device's pristine copy); the device pointers address the live copy.  The
+// ports-and-images forms: + the UsedPorts column (zero without a port dictionary), restored with the
+// rest on every run.  The volumes form: + vol_count / vol_attached (k_schedule's AssumePod targets).
+void pack_mutable(Packer& P, const kss_cluster* cl, DevJob& j, Form f) {
   const size_t N = (size_t)cl->n_nodes;
   j.c.requested = P.put(cl->requested, KSS_NRES * N);
   j.c.nonzero = P.put(cl->nonzero, 2 * N);
   j.c.pod_count = P.put(cl->pod_count, N);
   j.c.class_count = P.put(cl->class_count, (size_t)cl->n_classes * N);
   j.c.term_count = P.put(cl->term_count, (size_t)cl->n_terms * N);
-  if (pi) j.c.port_used = P.put<uint64_t>(cl->n_ports > 0 ? cl->port_used : nullptr, N);
-  if (vol) {
+  if (form_pi(f)) j.c.port_used = P.put<uint64_t>(cl->n_ports > 0 ? cl->port_used : nullptr, N);
+  if (form_vol(f)) {
     j.c.vol_count = P.put(cl->vol_count, (size_t)cl->n_vol_rows * N);
     j.c.vol_attached = P.put(cl->vol_attached, (size_t)cl->n_vol_keys * N);
   }
@@ -5610,23 +5638,6 @@ void vol_pack_host(const kss_cluster* cl, uint64_t* used, uint64_t* att, uint64_
   }
 }
 
-// The launch constants of one scenario (vol_pack_state's, from the scenario's own dictionaries).
-SVolLaunch vol_launch_consts(const kss_cluster* cl, const kss_profile& prof) {
-  SVolLaunch K{};
-  const uint32_t en = prof.filter_enabled;
-  for (int r = 0; r < cl->n_vol_rows && r < SV_ROWS; r++) {
-    const int k = cl->vol_row_key[r];
-    if (k >= 0 && k < SV_KEYS) K.keyrows[k] |= 1ull << r;
-  }
-  for (int k = 0; k < cl->n_vol_keys && k < SV_KEYS; k++) {
-    const int pl = cl->vol_key_plugin[k];
-    if ((en >> pl) & 1u) K.key_on |= 1u << k;
-    if (pl == KSS_F_NODE_VOLUME_LIMITS) K.key_csi |= 1u << k;
-  }
-  K.vr_on = (en >> KSS_F_VOLUME_RESTRICTIONS) & 1u;
-  return K;
-}
-
 }  // namespace
 
 struct kss_sweep {
@@ -5644,10 +5655,11 @@ struct kss_sweep {
   std::vector<int32_t> n_pods;
   int total_pods = 0, max_pods = 0, max_nodes = 0, max_keys = 0;
   bool simple = false;
-  bool form = false;  // the ports-and-images form (option sweep_ports_images): both columns packed
-  size_t sports_off = 0, podoff_off = 0;  // form on the k_simple family: SPort[total_pods + RING], int32[n_scen]
-  bool vform = false;     // some pod holds a volume program (option sweep_volumes): the volume columns packed
-  size_t vls_off = 0;     // ... on the k_simple family (the volumes form): SVolLaunch[n_scen]
+  // what is packed, whichever kernel runs (SweepPlan::form): the ports-and-images form (option sweep_ports_images), both
+  // columns; the volumes form (some pod holds a volume program, option sweep_volumes), the volume columns as well
+  Form form = FORM_PLAIN;
+  size_t sports_off = 0, podoff_off = 0;  // those forms on the k_simple family: SPort[total_pods + RING], int32[n_scen]
+  size_t vls_off = 0;     // the volumes form on the k_simple family: SVolLaunch[n_scen]
   int chunk = 0;
   Geometry g;
   PlanNeeds need;
@@ -5670,32 +5682,38 @@ extern "C" {
 //   - a pod with a volume program refuses the sweep unless the options sweep_ports_images and
 //     sweep_volumes are both on (then only a WaitForFirstConsumer claim does), and so does a pod with
 //     host ports or image rows while the option sweep_ports_images is 0;
-//   - vform: both options on and some scenario holds a volume pod.  Every scenario's volume columns
+//   - FORM_VOL: both options on and some scenario holds a volume pod.  Every scenario's volume columns
 //     are packed; on the k_simple family every scenario passed vol_form_admit on its own columns and
 //     the kernel is k_simple_vol_sweep, on the largest workgroup whose two slots per lane fit its LDS;
-//   - form: the option is on and some scenario holds such a pod.  Then every scenario gets records
-//     of the ports-and-images form (build_spods force: its 13-bit limit on raw NodeAffinity, zero
+//   - FORM_PI: the option is on and some scenario holds such a pod.  Then every scenario gets records
+//     of the ports-and-images form (simple_form ASK_SWEEP: its 13-bit limit on raw NodeAffinity, zero
 //     masks for pods without ports) and the kernel is k_simple_pi_sweep;
 //   - whatever keeps one scenario off the k_simple family (code, scen, pod: the first) puts the
 //     whole sweep on k_schedule, which reads the packed columns through DevCluster.
 // Needs no device.
 struct SweepPlan {
-  bool simple = false, form = false;
-  bool vform = false;  // options sweep_ports_images and sweep_volumes on and some scenario holds a volume pod
+  bool simple = false;
+  Form form = FORM_PLAIN;  // what is packed and, on the k_simple family, the kernel's form: independent of `simple`
   int code = GP_OK, scen = -1, pod = -1;  // why k_schedule / why refused, and where
   int total_pods = 0, max_pods = 0, max_nodes = 0, max_keys = 0;
   Geometry g;
   PlanNeeds need;
   std::vector<std::vector<SPod>> spods;  // simple: every scenario's records
-  std::vector<SPort> sports;             // simple && form: the masks in the order of `chosen`, + RING of padding
+  std::vector<SPort> sports;             // simple, the ports-and-images forms: the masks in the order of `chosen`, + RING of padding
   std::vector<int32_t> pod_off;          // ... and every scenario's first
-  std::vector<std::vector<SVol>> svols;  // simple && vform: every scenario's volume records
+  std::vector<std::vector<SVol>> svols;  // simple, the volumes form: every scenario's volume records
 };
 
 static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* clusters, const kss_podset* podsets,
                       SweepPlan& pl) {
   pl = SweepPlan{};
   const bool allow = opt(O_SWEEP_PI) != 0, allow_vol = allow && opt(O_SWEEP_VOL) != 0;
+  auto demote = [&](int code, int scen, int pod) {  // why k_schedule / why refused, and where
+    pl.code = code;
+    pl.scen = scen;
+    pl.pod = pod;
+    return 0;
+  };
   for (int s = 0; s < n_scen; s++) {
     pl.total_pods += podsets[s].n_pods;
     pl.max_pods = std::max(pl.max_pods, podsets[s].n_pods);
@@ -5709,22 +5727,18 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
         const kss_pod& p = podsets[s].pods[i];
         for (int e = 0; e < p.vol_len; e++)
           if (podsets[s].vols[p.vol_off + e].kind == KSS_VOL_BIND_WFFC) {
-            pl.scen = s;
-            pl.pod = i;
-            pl.code = GP_VOL_WFFC;
+            demote(GP_VOL_WFFC, s, i);
             return fail(KSS_E_UNSUPPORTED,
                         "scenario sweeps: pods with an unbound WaitForFirstConsumer claim take kss_schedule_batch, one "
                         "scenario at a time, whatever the option sweep_volumes says");
           }
       }
-      pl.vform = true;
+      pl.form = FORM_VOL;
     } else if (q.volumes || (q.ports_images && !allow)) {  // the first refusing pod; a volume pod before the others
       for (int i = 0; i < podsets[s].n_pods; i++) {
         const kss_pod& p = podsets[s].pods[i];
         if (q.volumes ? p.vol_len > 0 : pod_ports_images(p)) {
-          pl.scen = s;
-          pl.pod = i;
-          pl.code = GP_PORTS_IMAGES;
+          demote(GP_PORTS_IMAGES, s, i);
           if (q.volumes)
             return fail(KSS_E_UNSUPPORTED,
                         "scenario sweeps: pods with volumes (a volume program) take kss_schedule_batch, one scenario at a "
@@ -5735,7 +5749,7 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
         }
       }
     }
-    pl.form |= q.ports_images || (q.volumes && allow_vol);  // (the option is on; the volumes form is a variant of that form)
+    if (q.ports_images) pl.form = std::max(pl.form, FORM_PI);  // (the option is on, or the scenario was refused above)
   }
   // one workgroup per scenario: at most two node slots per lane (C5, 1,000 nodes: 512
   // threads ran the 512-scenario sweep in 16.5 ms against 23.7 ms at 256)
@@ -5745,25 +5759,20 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
   // k_static + k_simple for the whole sweep when every scenario qualifies (no spread /
   // inter-pod programs, no scalar resources, values inside the exact f64 envelope); in the form,
   // k_static_pi + k_simple_pi_sweep within that kernel's LDS
-  auto demote = [&](int code, int scen, int pod) {
-    pl.code = code;
-    pl.scen = scen;
-    pl.pod = pod;
-    return 0;
-  };
   // The volumes form costs 180 B of LDS per node slot (simple_lds_bytes_vol): two slots per lane of the
   // preferred workgroup may not fit.  In this form only, the largest workgroup (a multiple of 64 lanes,
   // at most the preference) whose geometry fits; none: k_schedule, on the preferred geometry.
-  if (pl.vform && !opt(O_NO_SIMPLE) && !simple_fits(pl.g, 0, true, true)) {
+  const bool vol = form_vol(pl.form);
+  if (vol && !opt(O_NO_SIMPLE) && !simple_fits(pl.g, 0, FORM_VOL)) {
     for (int t = (pref - 1) / 64 * 64; t >= 64; t -= 64) {
       Geometry g2;
-      if (pick_geometry(pl.max_nodes, 1, t, g2) && g2.threads <= pref && simple_fits(g2, 0, true, true)) {
+      if (pick_geometry(pl.max_nodes, 1, t, g2) && g2.threads <= pref && simple_fits(g2, 0, FORM_VOL)) {
         pl.g = g2;
         break;
       }
     }
   }
-  if (opt(O_NO_SIMPLE) || !simple_fits(pl.g, 0, pl.form, pl.vform)) return demote(GP_SWEEP_GEOMETRY, -1, -1);
+  if (opt(O_NO_SIMPLE) || !simple_fits(pl.g, 0, pl.form)) return demote(GP_SWEEP_GEOMETRY, -1, -1);
   if (pl.need.general) {
     for (int s = 0; s < n_scen; s++)
       for (int i = 0; i < podsets[s].n_pods; i++)
@@ -5774,15 +5783,15 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
   for (int i = 0; i < prof->fit_n; i++)
     if (!(prof->fit_weight[i] >= 0 && prof->fit_weight[i] < (1ll << 20))) return demote(GP_SWEEP_VALUES, -1, -1);
   pl.spods.resize((size_t)n_scen);
-  if (pl.vform) pl.svols.resize((size_t)n_scen);
-  if (pl.form) pl.sports.reserve((size_t)pl.total_pods + RING);
+  if (vol) pl.svols.resize((size_t)n_scen);
+  if (form_pi(pl.form)) pl.sports.reserve((size_t)pl.total_pods + RING);
   for (int s = 0; s < n_scen; s++) {
     const kss_cluster& cl = clusters[s];
     if (cl.n_scalar != 0) {
       // The volumes form only: extended resources that no pod of the scenario requests and the profile
       // does not score decide nothing (NodeResourcesFit checks the scalars a pod requests; attach limits
       // published as attachable-volumes-* are such columns), so the scenario runs with none.
-      bool idle = pl.vform && scalar_fast_ok(*prof, cl.n_scalar);
+      bool idle = vol && scalar_fast_ok(*prof, cl.n_scalar);
       for (int i = 0; i < podsets[s].n_pods && idle; i++)
         for (int r = 0; r < cl.n_scalar; r++)
           idle &= podsets[s].pods[i].fit_request[3 + r] == 0 && podsets[s].pods[i].commit_req[3 + r] == 0;
@@ -5798,25 +5807,20 @@ static int sweep_plan(const kss_profile* prof, int n_scen, const kss_cluster* cl
     // the volumes form: vol_form_admit per scenario, condition 4 on the scenario's own columns
     std::vector<int32_t> att_max, lim_max;
     VolAdmit va;
-    if (pl.vform) vol_admit_of(cl, att_max, lim_max, va);
-    if (!build_spods(&podsets[s], 0, pl.spods[s], nullptr, pl.form ? &pi : nullptr, false, pl.form, pl.vform ? &va : nullptr)) {
-      if (pl.vform && pi.vol_code != GP_OK) return demote(pi.vol_code, s, pi.vol_pod);  // the form's own reason
-      // (no programs, no volumes: fill_spod refused a pod's preferred NodeAffinity weights)
-      const int64_t lim = pl.form ? (int64_t)SWPI_NA_MAX : 0xFFFFF;
-      for (int i = 0; i < podsets[s].n_pods; i++) {
-        const int64_t wsum = pref_weight_sum(&podsets[s], podsets[s].pods[i]);
-        if (wsum > lim) return demote(wsum > 0xFFFFF ? GP_NA_WEIGHTS : GP_PI_NA_WEIGHTS, s, i);
-      }
-      return demote(GP_NA_WEIGHTS, s, -1);
-    }
-    if (pl.form) {
+    if (vol) vol_admit_of(cl, att_max, lim_max, va);
+    pi.form = pl.form;
+    if (!simple_form(&podsets[s], ASK_SWEEP, &va, pi)) return demote(pi.vol_code, s, pi.vol_pod);  // the form's own reason
+    // (no programs, no volumes the form does not take: fill_spod refused a pod's preferred NodeAffinity weights)
+    if (!build_spods(&podsets[s], 0, pl.spods[s], pi))
+      return demote(pi.misfit == POD_NA_FORM ? GP_PI_NA_WEIGHTS : GP_NA_WEIGHTS, s, pi.fail_pod);
+    if (form_pi(pl.form)) {
       pl.pod_off.push_back((int32_t)pl.sports.size());
       pl.sports.insert(pl.sports.end(), pi.ports.begin(), pi.ports.begin() + podsets[s].n_pods);
     }
-    if (pl.vform) pl.svols[s].swap(pi.vols);
+    if (vol) pl.svols[s].swap(pi.vols);
   }
   // the ring's prefetch distance of padding: the last scenario's prefetch stays inside the allocation
-  if (pl.form) pl.sports.resize((size_t)pl.total_pods + RING, SPort{});
+  if (form_pi(pl.form)) pl.sports.resize((size_t)pl.total_pods + RING, SPort{});
   pl.simple = true;
   return 0;
 }
@@ -5846,11 +5850,10 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   sw->need = pl.need;
   sw->g = pl.g;
   sw->simple = pl.simple;
-  sw->form = pl.form;
-  sw->vform = pl.vform;
-  const bool simple = pl.simple, form = pl.form, vform = pl.vform;
+  const Form form = sw->form = pl.form;
+  const bool simple = pl.simple, pi_simple = simple && form_pi(form), vol_simple = simple && form_vol(form);
   // the volumes form's per-scenario pieces: lim columns and SVol records (inputs), used / att (mutable)
-  std::vector<SVolLaunch> vls(vform && simple ? (size_t)n_scen : 0);
+  std::vector<SVolLaunch> vls(vol_simple ? (size_t)n_scen : 0);
   auto pack_vol_inputs = [&](Packer& P, int s) {
     const size_t N = (size_t)std::max(clusters[s].n_nodes, 1);
     vls[(size_t)s].lim = P.put<uint64_t>(nullptr, 2 * N);
@@ -5872,25 +5875,25 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   Packer dry;
   for (int s = 0; s < n_scen; s++) {
     in_off[s] = dry.o;
-    pack_inputs(dry, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form, vform);
-    if (vform && simple) pack_vol_inputs(dry, s);
+    pack_inputs(dry, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form);
+    if (vol_simple) pack_vol_inputs(dry, s);
   }
   sw->pristine_off = dry.o;
   for (int s = 0; s < n_scen; s++) {
     mut_off[s] = dry.o;
-    pack_mutable(dry, &clusters[s], jobs[s], form, vform);
-    if (vform && simple) pack_vol_mutable(dry, s);
+    pack_mutable(dry, &clusters[s], jobs[s], form);
+    if (vol_simple) pack_vol_mutable(dry, s);
   }
   sw->mut_bytes = dry.o - sw->pristine_off;
   sw->jobs_off = dry.o;
   dry.put<DevJob>(nullptr, (size_t)n_scen);
-  if (form && simple) {
+  if (pi_simple) {
     dry.put<SPort>(nullptr, pl.sports.size());
     sw->sports_off = dry.last;
     dry.put<int32_t>(nullptr, (size_t)n_scen);
     sw->podoff_off = dry.last;
   }
-  if (vform && simple) {
+  if (vol_simple) {
     dry.put<SVolLaunch>(nullptr, (size_t)n_scen);
     sw->vls_off = dry.last;
   }
@@ -5913,7 +5916,7 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   // k_static time it hides when both share the CUs)
   if (simple) hipSetDevice(device);  // the budget follows this device's free memory
   sw->chunk = simple ? static_chunk(sum_nodes, sw->max_pods) : 0;
-  const bool dbl = simple && !vform && sw->chunk < sw->max_pods && opt(O_SWEEP_PIPE) != 0;  // (the volumes form: one stream)
+  const bool dbl = simple && !form_vol(form) && sw->chunk < sw->max_pods && opt(O_SWEEP_PIPE) != 0;  // (the volumes form: one stream)
   if (dbl) sw->chunk = static_chunk(2 * sum_nodes, sw->max_pods);
   const int halves = dbl ? 2 : 1;
   if (simple) {
@@ -5942,21 +5945,18 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
   auto work = [&](int t) {
     for (int s = t; s < n_scen; s += nth) {
       Packer P{img.get(), sw->arena, in_off[s]};
-      pack_inputs(P, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form, vform);
-      if (vform && simple) {
+      pack_inputs(P, &clusters[s], &podsets[s], simple ? &spods[s] : nullptr, jobs[s], form);
+      if (vol_simple) {
         pack_vol_inputs(P, s);
         jobs[s].c.n_scalar = 0;  // (sweep_plan: its extended resources are idle; the loop keeps no scalar columns)
       }
       // host bytes at the pristine position, device pointers at the live position
       Packer M{img.get(), sw->arena + (sw->live_off - sw->pristine_off), mut_off[s]};
-      pack_mutable(M, &clusters[s], jobs[s], form, vform);
-      if (vform && simple) {
+      pack_mutable(M, &clusters[s], jobs[s], form);
+      if (vol_simple) {
         pack_vol_mutable(M, s);
-        const SVolLaunch K = vol_launch_consts(&clusters[s], *prof);
-        for (int k = 0; k < SV_KEYS; k++) vls[(size_t)s].keyrows[k] = K.keyrows[k];
-        vls[(size_t)s].key_on = K.key_on;
-        vls[(size_t)s].key_csi = K.key_csi;
-        vls[(size_t)s].vr_on = K.vr_on;
+        vol_launch_consts(vls[(size_t)s], clusters[s].vol_row_key, clusters[s].n_vol_rows, clusters[s].vol_key_plugin,
+                          clusters[s].n_vol_keys, *prof);
       }
       DevJob& j = jobs[s];
       j.n_pods = podsets[s].n_pods;
@@ -5985,11 +5985,11 @@ kss_sweep* kss_sweep_create(int32_t device, const kss_profile* prof, int32_t n_s
     }
   }
   memcpy(img.get() + sw->jobs_off, jobs.data(), sizeof(DevJob) * n_scen);
-  if (form && simple) {
+  if (pi_simple) {
     memcpy(img.get() + sw->sports_off, pl.sports.data(), sizeof(SPort) * pl.sports.size());
     memcpy(img.get() + sw->podoff_off, pl.pod_off.data(), sizeof(int32_t) * pl.pod_off.size());
   }
-  if (vform && simple) memcpy(img.get() + sw->vls_off, vls.data(), sizeof(SVolLaunch) * vls.size());
+  if (vol_simple) memcpy(img.get() + sw->vls_off, vls.data(), sizeof(SVolLaunch) * vls.size());
   if (hipMemcpy(sw->arena, img.get(), sw->up_bytes, hipMemcpyHostToDevice) != hipSuccess) {
     fail(KSS_E_DEVICE, "sweep upload failed");
     return nullptr;
@@ -6027,9 +6027,10 @@ int kss_sweep_run(kss_sweep* sw, int32_t* chosen_out, double* device_ms) {
     L.prof = &sw->prof, L.st2 = sw->st2, L.pev = &sw->pev;
     L.n_pods = sw->max_pods, L.max_nodes = sw->max_nodes, L.chunk = sw->chunk;
     L.n_keys = sw->max_keys, L.err = err;
-    if (sw->form) L.sports = reinterpret_cast<const SPort*>(sw->arena + sw->sports_off);
-    if (sw->form) L.pod_off = reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off);
-    if (sw->vform) L.vl = reinterpret_cast<const SVolLaunch*>(sw->arena + sw->vls_off);
+    L.form = sw->form, L.sweep = true;
+    if (form_pi(sw->form)) L.sports = reinterpret_cast<const SPort*>(sw->arena + sw->sports_off);
+    if (form_pi(sw->form)) L.pod_off = reinterpret_cast<const int32_t*>(sw->arena + sw->podoff_off);
+    if (form_vol(sw->form)) L.vl = reinterpret_cast<const SVolLaunch*>(sw->arena + sw->vls_off);
     rc = launch_simple(st, L);
   } else
     rc = launch_schedule(st, sw->g, sw->n_scen, sw->need.bins_cap + (sw->prof.pct_nodes_to_score < 100 ? 1 : 0),
@@ -6067,7 +6068,7 @@ int kss_sweep_info(kss_sweep* sw, double* stage_ms, int32_t* kernel, int64_t* up
 
 int kss_sweep_form(kss_sweep* sw) {
   if (!sw) return fail(KSS_E_INVAL, "null sweep");
-  return sw->vform ? 2 : (sw->form ? 1 : 0);  // 2: a volume program somewhere, the volume columns packed as well
+  return (int)sw->form;  // 2: a volume program somewhere, the volume columns packed as well
 }
 
 void kss_sweep_destroy(kss_sweep* sw) {
@@ -6466,7 +6467,8 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   std::vector<int32_t> att_max, lim_max;
   VolAdmit va;
   vol_admit_of(*cl, att_max, lim_max, va);
-  if (build_spods(ps, cl->n_scalar, sp, nullptr, &pi, false, false, &va)) {
+  simple_form(ps, ASK_BATCH, &va, pi);
+  if (build_spods(ps, cl->n_scalar, sp, pi)) {
     out3[0] = 1;
     return 0;
   }
@@ -6479,8 +6481,8 @@ int kss_plan_podset(const kss_cluster* cl, const kss_podset* ps, int32_t* out3) 
   }
   out3[1] = need.fail_pod;
   out3[2] = need.fail_code;
-  if (pi.form && pi.na_pod >= 0 && need.fail_code == GP_PORTS_IMAGES) {  // the form's own limit kept it off k_simple
-    out3[1] = pi.na_pod;
+  if (pi.misfit == POD_NA_FORM && ps->pods[pi.fail_pod].vol_len == 0 && need.fail_code == GP_PORTS_IMAGES) {
+    out3[1] = pi.fail_pod;  // the form's own limit kept it off k_simple
     out3[2] = GP_PI_NA_WEIGHTS;
   }
   if (pi.vol_code != GP_OK && need.fail_code == GP_PORTS_IMAGES) {  // the volumes form refused the batch: its reason
@@ -6503,10 +6505,10 @@ int kss_plan_podset_ex(const kss_cluster* cl, const kss_podset* ps, const kss_pr
     if (ps->pods[i].names_len >= 0) names_pod = i;
   const bool win = num_feasible_to_find(cl->n_nodes, prof->pct_nodes_to_score) < cl->n_nodes;
   const bool spread_def = out3[0] == 2 && spread_window_profile_ok(*prof);
-  // k_simple's volumes form (the plan above admitted the batch to it) runs the window only with the
-  // option simple_volumes_window
+  // k_simple's volumes form (a k_simple answer for a batch with a volume pod is of that form): still
+  // allowed under the window, as the run will ask?  The first pod with a volume program otherwise.
   int vol_pod = -1;
-  if (out3[0] == 1 && !opt(O_SIMPLE_VOL_WIN))
+  if (out3[0] == 1 && !simple_form_allowed(FORM_VOL, win, false))
     for (int i = 0; i < ps->n_pods && vol_pod < 0; i++)
       if (ps->pods[i].vol_len > 0) vol_pod = i;
   if (win && vol_pod >= 0) {
@@ -6541,18 +6543,15 @@ int kss_plan_service(const kss_cluster* cl, const kss_podset* ps, const kss_prof
     out3[2] = code;
     return 0;
   };
-  bool form = false;  // the ports-and-images form: some pod needs it and the option allows it
-  if (opt(O_SERVICE_PI))
-    for (int i = 0; i < ps->n_pods; i++) form |= pod_ports_images(ps->pods[i]);
+  Form f = FORM_PLAIN;  // the ports-and-images form: some pod needs it and the option allows it
+  for (int i = 0; i < ps->n_pods; i++)
+    if (pod_ports_images(ps->pods[i]) && service_form_allowed(FORM_PI)) f = FORM_PI;
   int names_pod = -1;
   for (int i = 0; i < ps->n_pods; i++) {  // the first refusing pod, as build_spods walks them
     const kss_pod& p = ps->pods[i];
     if (p.n_hard | p.n_soft | p.ipa_len) return refuse(GP_SVC_PROGRAMS, i);
-    if (p.vol_len > 0) return refuse(GP_SVC_VOLUMES, i);
-    if (!form && pod_ports_images(p)) return refuse(GP_SVC_PORTS_IMAGES, i);
-    const int64_t wsum = pref_weight_sum(ps, p);
-    if (wsum > 0xFFFFF) return refuse(GP_NA_WEIGHTS, i);
-    if (form && wsum > (int64_t)SWPI_NA_MAX) return refuse(GP_SVC_PI_NA_WEIGHTS, i);
+    static const int code[POD_N] = {GP_OK, GP_SVC_VOLUMES, GP_SVC_PORTS_IMAGES, GP_NA_WEIGHTS, GP_SVC_PI_NA_WEIGHTS};
+    if (const PodMisfit m = pod_misfit(ps, p, f)) return refuse(code[m], i);
     if (names_pod < 0 && p.names_len >= 0) names_pod = i;
   }
   if (cl->n_scalar != 0) return refuse(GP_SVC_SCALAR, ps->n_pods > 0 ? 0 : -1);
@@ -6573,7 +6572,7 @@ int kss_plan_sweep(const kss_profile* prof, int32_t n_scen, const kss_cluster* c
   SweepPlan pl;
   const int rc = sweep_plan(prof, n_scen, clusters, podsets, pl);
   out[0] = pl.simple ? 1 : 0;
-  out[1] = pl.vform ? 2 : (pl.form ? 1 : 0);
+  out[1] = (int)pl.form;
   out[2] = pl.scen;
   out[3] = pl.pod;
   return rc ? rc : pl.code;

@@ -585,6 +585,21 @@ def test_list_without_ports_or_images_runs_what_it_ran():
     s.close()
 
 
+def test_option_turned_off_between_stage_and_start():
+    """The option is process-wide and read twice: at the stage (records of the form) and again when
+    the service starts.  Turned off in between, the service runs its general chain (mode 0), with the
+    oracle's records and final state."""
+    cc, cp, ch_o, res, st = _fuzz((3, 12, 10, 30), 100)
+    prof = _prof()
+    native.set_option("service_ports_images", 1)
+    assert native.plan_service(cc.as_struct(), cp.as_struct(), prof)["chain"] == 1
+    svc = _ctx(cc, prof)
+    svc.stage(cp.as_struct())
+    native.set_option("service_ports_images", 0)
+    svc.service_start()
+    _service(cc, cp, prof, res, st, mode_pi=False, svc=svc).close()
+
+
 @pytest.mark.parametrize("how", ["service_general", "svc_no_static", "volume-pod"])
 def test_lists_that_keep_the_general_chain(how):
     """With the option on: service_general forces mode 0, a list without the static-word table keeps

@@ -350,6 +350,29 @@ def test_option_off_runs_k_schedule():
     _run(cc, cp, ch_o, res, st, kernel="k_schedule")
 
 
+def test_option_turned_off_between_stage_and_run():
+    """The option is process-wide and read twice: at the stage (records of the form) and again at the
+    run.  Turned off in between, the staged batch runs on k_schedule, with the oracle's results."""
+    cc, cp, ch_o, res, st = _fuzz(3)
+    N = cc.n_nodes
+    native.set_option("simple_ports_images", 1)
+    assert native.plan_podset(cc.as_struct(), cp.as_struct())["kernel"] == "k_simple"
+    ctx = native.Context(abi.default_profile())
+    ctx.load(cc.as_struct())
+    ctx.stage(cp.as_struct())
+    native.set_option("simple_ports_images", 0)
+    chosen = ctx.run_staged(cp.n)
+    assert ctx.last_kernel() == "k_schedule"
+    np.testing.assert_array_equal(chosen, ch_o)
+    _meta_equal(ctx.fetch_meta(cp.n), res, cp.n)
+    np.testing.assert_array_equal(ctx.port_state(), st["port_used"][:N])
+    g = ctx.node_state()
+    np.testing.assert_array_equal(g["requested"][:, :N], st["requested"][:, :N])
+    np.testing.assert_array_equal(g["nonzero"][:, :N], st["nonzero"][:, :N])
+    np.testing.assert_array_equal(g["pod_count"][:N], st["pod_count"][:N])
+    ctx.close()
+
+
 def test_batch_without_ports_or_images_is_untouched():
     nodes, bound, pods = progfuzz.make(2, 300, 300, extended=False, programs=False)
     cc, cp, _ = compile_cluster(nodes, bound, pods)

@@ -327,3 +327,28 @@ def test_state_hand_over():
     np.testing.assert_array_equal(vc2, vc1)
     np.testing.assert_array_equal(va2, va1)
     ctx.close()
+
+
+# --------------------------------------------------------------------------------------
+# 8. the option turned off between the stage and the run
+# --------------------------------------------------------------------------------------
+def test_option_turned_off_between_stage_and_run():
+    """simple_volumes is process-wide and read twice: at the stage (records of the volumes form) and
+    again at the run.  Turned off in between, the staged batch runs on k_schedule, with the oracle's
+    results."""
+    cc, cp, ch_o, res, fin, r = _fuzz(2)
+    _assert_reach(r)
+    native.set_option("simple_ports_images", 1)
+    native.set_option("simple_volumes", 1)
+    assert native.plan_podset(cc.as_struct(), cp.as_struct())["kernel"] == "k_simple"
+    ctx = native.Context(abi.default_profile())
+    ctx.load(cc.as_struct())
+    ctx.stage(cp.as_struct())
+    native.set_option("simple_volumes", 0)
+    chosen = ctx.run_staged(cp.n)
+    f = ctx.last_simple_form()
+    assert ctx.last_kernel() == "k_schedule" and f == {"volumes": 0, "lds_bytes": 0}, (ctx.last_kernel(), f)
+    np.testing.assert_array_equal(chosen, ch_o)
+    _meta_equal(ctx.fetch_meta(cp.n), res, cp.n)
+    _state_equal(ctx, cc, fin)
+    ctx.close()

@@ -304,3 +304,28 @@ def test_second_batch_continues(second):
     _meta_equal(ctx.fetch_meta(cp.n - n1), res, cp.n - n1, first=n1)
     _state_equal(ctx, cc, fin)
     ctx.close()
+
+
+# --------------------------------------------------------------------------------------
+# 7. the option turned off between the stage and the run
+# --------------------------------------------------------------------------------------
+def test_option_turned_off_between_stage_and_run():
+    """simple_volumes_window is process-wide and read at the run (the stage builds the volumes form's
+    records whatever it says).  Turned off between the stage and the run, the staged batch runs the
+    window on k_schedule, with the oracle's results and nextStartNodeIndex."""
+    cc, cp, prof, ch_o, res, fin, r, w = _case("vol", MID, 30)
+    _assert_recorded("vol", MID, 30, r, w)
+    native.set_option("simple_ports_images", 1)
+    native.set_option("simple_volumes", 1)
+    native.set_option("simple_volumes_window", 1)
+    assert native.plan_podset(cc.as_struct(), cp.as_struct(), prof)["kernel"] == "k_simple"
+    ctx = native.Context(prof)
+    ctx.load(cc.as_struct())
+    ctx.stage(cp.as_struct())
+    native.set_option("simple_volumes_window", 0)
+    chosen = ctx.run_staged(cp.n)
+    _ran(ctx, False)
+    np.testing.assert_array_equal(chosen, ch_o)
+    _meta_equal(ctx.fetch_meta(cp.n), res, cp.n)
+    _state_equal(ctx, cc, fin)
+    ctx.close()

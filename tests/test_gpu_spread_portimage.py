@@ -36,6 +36,7 @@ REACH = {
     (2, 300, 300, False, 50): (237, 76, 27, 175, 293),
     (20, 211, 150, False, 50): (138, 38, 23, 77, 138),
     (2, 300, 300, True, 0): (235, 74, 28, 172, 291),
+    (1, 12, 40, True, 100): (31, 6, 4, 18, 20),
 }
 
 
@@ -354,6 +355,22 @@ def test_word_edges(shards):
 def test_option_off_runs_k_schedule():
     cc, cp, ch_o, res, st = _fuzz(4, 5, 40)
     _run(cc, cp, ch_o, res, st, kernel="k_schedule", on=0)
+
+
+def test_option_turned_off_between_stage_and_run():
+    """The option is process-wide and read twice: at the stage (records of the form) and again at the
+    run.  Turned off in between, the staged batch runs on k_schedule, with the oracle's results."""
+    cc, cp, ch_o, res, st = _fuzz(1, 12, 40)
+    native.set_option("spread_ports_images", 1)
+    assert native.plan_podset(cc.as_struct(), cp.as_struct())["kernel"] == "k_spread"
+    ctx = native.Context(abi.default_profile())
+    ctx.load(cc.as_struct())
+    ctx.stage(cp.as_struct())
+    native.set_option("spread_ports_images", 0)
+    chosen = ctx.run_staged(cp.n)
+    assert ctx.last_kernel() == "k_schedule" and ctx.last_spread_form() == (0, 0), (ctx.last_kernel(), ctx.last_spread_form())
+    _check(ctx, cc, cp, ch_o, res, st, chosen)
+    ctx.close()
 
 
 def test_ungrafted_batch_is_untouched():

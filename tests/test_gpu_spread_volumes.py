@@ -39,6 +39,7 @@ REACH_MORE = {
     (2, 300, 300, False, 50): (221, 49, 105, 17, 168, 279, 74, 83),
     (20, 211, 150, False, 50): (130, 14, 47, 15, 71, 133, 37, 42),
     (2, 300, 300, True, 0): (219, 48, 101, 17, 165, 276, 73, 80),
+    (4, 12, 40, True, 100): (36, 2, 11, 3, 16, 13, 7, 9),
 }
 
 
@@ -460,6 +461,25 @@ def test_word_edges(shards):
 def test_option_off_runs_k_schedule():
     cc, cp, ch_o, res, st = _fuzz(1, 60, 200)
     _run(cc, cp, ch_o, res, st, form=False, on=0)
+
+
+def test_option_turned_off_between_stage_and_run():
+    """spread_volumes is process-wide and read twice: at the stage (records of the volumes form) and
+    again at the run.  Turned off in between, the staged batch runs on k_schedule, with the oracle's
+    results."""
+    cc, cp, ch_o, res, st = _fuzz(4, 12, 40)
+    native.set_option("spread_ports_images", 1)
+    native.set_option("spread_volumes", 1)
+    assert native.plan_podset(cc.as_struct(), cp.as_struct())["kernel"] == "k_spread"
+    ctx = native.Context(abi.default_profile())
+    ctx.load(cc.as_struct())
+    ctx.stage(cp.as_struct())
+    native.set_option("spread_volumes", 0)
+    chosen = ctx.run_staged(cp.n)
+    f = ctx.last_spread_form()
+    assert ctx.last_kernel() == "k_schedule" and f == (0, 0), (ctx.last_kernel(), f)
+    _check(ctx, cc, cp, ch_o, res, st, chosen)
+    ctx.close()
 
 
 def test_batch_without_volume_pods_is_untouched():
